@@ -31,6 +31,23 @@ first-occurrence ordering of the final table on device.  Text is generated on
 the device once before timing (synthetic data: a Zipf(1.0) vocabulary of 100k
 words); nothing inside the timed region is cached between steps (the table is
 cleared at the start of every step).
+
+A plain run does only what the headline needs: set-up, warm-up, the timed
+steps, `--dump-outputs` if asked for, the result line.  `--full` adds what
+takes work of its own: the validation of the final table (token sum, and key
+for key against the CPU oracle that walks the synthetic generator) with the
+exit status it decides, `"stages"` (device time per stage, from one more
+untimed step with the stage marks on) and `"runtime"` (the HIP / RCCL /
+engine objects mapped into the rank).
+
+`--dump-outputs DIR` writes what the last timed step computed, as a caller of
+`Engine.result()` receives it (the table in first-occurrence order), to
+`DIR/<name>.npy`: `counts`, `first_offsets`, `word_lengths`, `total` (tokens,
+distinct words; all float64, exact below 2^53) and `word_bytes` (float32, the
+words' bytes back to back).  Above 64 MB in
+all, a fixed seeded sample of the rows is written and `rows.npy` holds their
+row numbers.  The input is a function of the arguments alone, so two builds
+run with the same arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -62,8 +79,14 @@ def parse(argv=None):
     ap.add_argument("--merge", choices=["shuffle", "dense"], default=None,
                     help="cross-GPU merge: shuffle (all-to-all to hash owners) or dense (reduce-scatter + all-gather);"
                          " default: the config's")
+    ap.add_argument("--full", action="store_true",
+                    help="also validate the final table (token sum + key for key against the CPU oracle; decides the "
+                         "exit status) and report \"stages\" (one more untimed step) and \"runtime\"")
     ap.add_argument("--no-oracle", action="store_true",
-                    help="skip the key-for-key check against the generator-walk oracle (sum check only)")
+                    help="with --full: skip the key-for-key check against the generator-walk oracle (sum check only)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the last timed step's table (what Engine.result() returns) as DIR/<name>.npy, "
+                         "float32 / float64, at most 64 MB in all")
     ap.add_argument("--json-out", default="")
     ap.add_argument("--virtual-ranks", type=int, default=0,
                     help="W > 0: W engines (threads) on GPU 0 with the stream-ordered loopback communicator, each "
@@ -114,6 +137,40 @@ def loaded_runtime() -> dict:
     return {k: sorted(v) if isinstance(v, set) else v for k, v in libs.items()}
 
 
+DUMP_BUDGET = 64 * 1000 * 1000  # bytes of array data in all
+
+
+def dump_outputs(res, out_dir: str) -> dict:
+    """The table of the last timed step as float .npy files (at most DUMP_BUDGET bytes)."""
+    import numpy as np
+
+    n = len(res.words)
+    lengths = np.fromiter((len(w) for w in res.words), dtype=np.int64, count=n)
+    rows = np.arange(n)
+    per_row = 3 * 8  # counts, first_offsets, word_lengths
+    need = n * per_row + 4 * int(lengths.sum())
+    sampled = need > DUMP_BUDGET
+    if sampled:
+        # a fixed, seeded sample of the rows, small enough whatever their words' lengths
+        k = int(DUMP_BUDGET // (per_row + 8 + 4 * max(int(lengths.max()), 1)))
+        rows = np.sort(np.random.default_rng(12345).choice(n, size=k, replace=False))
+    blob = b"".join(res.words[i] for i in rows) if sampled else b"".join(res.words)
+    arrays = {
+        "counts": np.asarray(res.counts, dtype=np.float64)[rows],
+        "first_offsets": np.asarray(res.first_off, dtype=np.float64)[rows],
+        "word_lengths": lengths[rows].astype(np.float64),
+        "word_bytes": np.frombuffer(blob, dtype=np.uint8).astype(np.float32),
+        "total": np.asarray([float(res.total), float(n)], dtype=np.float64),  # tokens, distinct words
+    }
+    if sampled:
+        arrays["rows"] = rows.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, arr in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+    return {"dir": out_dir, "rows": int(len(rows)), "of": n, "sampled": bool(sampled),
+            "bytes": int(sum(x.nbytes for x in arrays.values()))}
+
+
 def run_virtual(a) -> int:
     """--virtual-ranks W: the merged step at world size W on one GPU (all ranks share it)."""
     from cuda_mapreduce_amd.models import CONFIGS
@@ -160,6 +217,8 @@ def run_virtual(a) -> int:
                    "merge": merge, "vocab": vocab, "long_frac": long_frac,
                    "communicator": "stream-ordered loopback (src/dist/comm.cpp)"},
     }
+    if a.dump_outputs:
+        out["dumped"] = dump_outputs(res, a.dump_outputs)
     line = json.dumps(out)
     print(line, flush=True)
     if a.json_out:
@@ -275,41 +334,48 @@ def run_rank(a) -> int:
         keys = step()
     barrier()
     dt = time.perf_counter() - t0
-    eng.set_stage_events(True)
-    step()
-    st = eng.stats()
     ms = dt / max(a.steps, 1) * 1e3
-    tokens = st["tokens"]
+    tokens = eng.stats()["tokens"]  # counted by the map kernels of the last timed step
     if comm is not None:
         ms = comm.allreduce_f64([ms], "max")[0]
         tokens_total = comm.allreduce_f64([float(tokens)], "sum")[0]
     else:
         tokens_total = float(tokens)
-    # Validation (untimed): the merged table must equal, key for key (words,
-    # first-occurrence order, counts, first offsets, total), the exact table of
-    # the whole logical stream computed on the CPU from the synthetic
-    # generator's own word walk — independent of every GPU stage and of any
-    # tokenizer; and its counts must sum to the words the map kernels counted.
-    res = eng.result(comm)
+    # the last timed step's table on the host (rank 0's is the merged one): only
+    # when something reads it
+    res = eng.result(comm) if (a.full or a.dump_outputs) else None
+    dumped = None
+    if a.dump_outputs and rank == 0:
+        dumped = dump_outputs(res, a.dump_outputs)
+    st = None
     valid = True
     check = {}
-    if rank == 0:
-        valid = int(res.total) == int(tokens_total) and int(res.counts.sum()) == int(tokens_total)
-        if not valid:
-            print(f"bench: VALIDATION FAILED: table total {int(res.total)} (rows sum {int(res.counts.sum())}) "
-                  f"!= tokens {int(tokens_total)}", file=sys.stderr, flush=True)
-        if not a.no_oracle:
-            t1 = time.perf_counter()
-            want = synthetic_oracle(world, nbytes, seed, vocab, zipf, pool_bytes=pool_bytes, chunk=chunk,
-                                    long_frac=long_frac)
-            diff = compare_results(res, want)
-            check = {"oracle": "generator word walk (cpu_count_synth)", "identical": not diff,
-                     "seconds": round(time.perf_counter() - t1, 2)}
-            if diff:
-                valid = False
-                print(f"bench: VALIDATION FAILED vs oracle: {diff}", file=sys.stderr, flush=True)
-    if comm is not None:  # every rank exits with rank 0's verdict
-        valid = comm.allreduce_f64([0.0 if valid else 1.0], "max")[0] == 0.0
+    if a.full:
+        eng.set_stage_events(True)
+        step()
+        st = eng.stats()
+        # Validation (untimed): the merged table must equal, key for key (words,
+        # first-occurrence order, counts, first offsets, total), the exact table of
+        # the whole logical stream computed on the CPU from the synthetic
+        # generator's own word walk — independent of every GPU stage and of any
+        # tokenizer; and its counts must sum to the words the map kernels counted.
+        if rank == 0:
+            valid = int(res.total) == int(tokens_total) and int(res.counts.sum()) == int(tokens_total)
+            if not valid:
+                print(f"bench: VALIDATION FAILED: table total {int(res.total)} (rows sum {int(res.counts.sum())}) "
+                      f"!= tokens {int(tokens_total)}", file=sys.stderr, flush=True)
+            if not a.no_oracle:
+                t1 = time.perf_counter()
+                want = synthetic_oracle(world, nbytes, seed, vocab, zipf, pool_bytes=pool_bytes, chunk=chunk,
+                                        long_frac=long_frac)
+                diff = compare_results(res, want)
+                check = {"oracle": "generator word walk (cpu_count_synth)", "identical": not diff,
+                         "seconds": round(time.perf_counter() - t1, 2)}
+                if diff:
+                    valid = False
+                    print(f"bench: VALIDATION FAILED vs oracle: {diff}", file=sys.stderr, flush=True)
+        if comm is not None:  # every rank exits with rank 0's verdict
+            valid = comm.allreduce_f64([0.0 if valid else 1.0], "max")[0] == 0.0
     total_bytes = nbytes * world
     gbps = total_bytes / (ms / 1e3) / 1e9
     words = tokens_total / (ms / 1e3)
@@ -331,8 +397,6 @@ def run_rank(a) -> int:
             "dtype": "u8 text / u64 counts",
             "data": data,
             "words_per_s": round(words, 1),
-            "validated": valid,
-            "validation": check or {"oracle": "skipped (--no-oracle): token-sum check only"},
             "distinct_words": keys,
             "config": {
                 "model": f"wordcount-mapreduce/{cfg.name}",
@@ -344,9 +408,14 @@ def run_rank(a) -> int:
                 "merge": merge,
             },
             "control_plane": "native RCCL communicator (file rendezvous), no torch" if comm else "single process",
-            "runtime": loaded_runtime(),
-            "stages": st,  # from one extra untimed step with the stage marks on
         }
+        if a.full:
+            out["validated"] = valid
+            out["validation"] = check or {"oracle": "skipped (--no-oracle): token-sum check only"}
+            out["runtime"] = loaded_runtime()
+            out["stages"] = st  # from one extra untimed step with the stage marks on
+        if dumped:
+            out["dumped"] = dumped
         if pool_info:
             out["host_pool"] = pool_info
         line = json.dumps(out)

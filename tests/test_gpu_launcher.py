@@ -20,7 +20,7 @@ def test_torchrun_world1_rccl_merge(merge):
     port = 29500 + random.randint(100, 900)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"),
-           "--gpus", "1", "--steps", "2", "--warmup", "1", "--gb-per-gpu", "0.125", "--merge", merge]
+           "--gpus", "1", "--steps", "2", "--warmup", "1", "--gb-per-gpu", "0.125", "--merge", merge, "--full"]
     p = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=110)
     assert p.returncode == 0, p.stderr[-3000:]
     line = [l for l in p.stdout.splitlines() if l.startswith("{")][-1]
@@ -49,7 +49,8 @@ def test_bench_one_runtime_per_rank():
     # the rank loads only /opt/rocm's HIP runtime and RCCL (no torch, no second copy)
     env = dict(os.environ, WC_MERGE_ALWAYS="1")
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
-                        "--gb-per-gpu", "0.125"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=110)
+                        "--gb-per-gpu", "0.125", "--full"], cwd=ROOT, env=env, capture_output=True, text=True,
+                       timeout=110)
     assert p.returncode == 0, p.stderr[-3000:]
     d = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
     rt = d["runtime"]
@@ -108,3 +109,40 @@ def test_bench_refuses_more_local_ranks_than_gpus():
                        cwd=ROOT, env=env, capture_output=True, text=True, timeout=60)
     assert p.returncode == 2
     assert "one rank per GPU" in p.stderr
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_is_lean_and_dumps_its_outputs(tmp_path):
+    """A plain run times its steps and prints the headline only (what takes work
+    of its own is behind --full); --dump-outputs writes the last timed step's
+    table as float arrays, equal to the CPU oracle's table of the same input."""
+    import numpy as np
+
+    from cuda_mapreduce_amd.ops import cpu_count_synth
+
+    out = tmp_path / "dump"
+    gb, vocab = 1 / 64, 5000
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                        "--gb-per-gpu", str(gb), "--vocab", str(vocab), "--dump-outputs", str(out)],
+                       cwd=ROOT, capture_output=True, text=True, timeout=110)
+    assert p.returncode == 0, p.stderr[-3000:]
+    d = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0
+    assert d["metric"] == "GB/s text ingested (whole node)" and d["unit"] == "GB/s" and d["higher_is_better"] is True
+    nbytes = d["config"]["bytes_per_gpu"]
+    assert nbytes == int(gb * (1 << 30))
+    # value = bytes / step time; both are printed rounded (3 and 4 decimals)
+    ms = d["ms_per_step"]
+    assert abs(d["value"] - nbytes / (ms / 1e3) / 1e9) <= d["value"] * (0.5e-4 / (ms - 0.5e-4)) * 1.01 + 0.5e-3
+    for k in ("validated", "validation", "stages", "runtime"):
+        assert k not in d, k
+    want = cpu_count_synth(nbytes, 0, 1, vocab, 1.0)
+    arr = {f[:-4]: np.load(out / f) for f in sorted(os.listdir(out))}
+    assert sorted(arr) == ["counts", "first_offsets", "total", "word_bytes", "word_lengths"]
+    assert all(a.dtype in (np.float32, np.float64) for a in arr.values())
+    assert sum(a.nbytes for a in arr.values()) <= 64 * 1000 * 1000
+    assert arr["total"].tolist() == [float(want.total), float(len(want))]
+    assert np.array_equal(arr["counts"], want.counts.astype(np.float64))
+    assert np.array_equal(arr["first_offsets"], want.first_off.astype(np.float64))
+    assert np.array_equal(arr["word_lengths"], np.array([len(w) for w in want.words], np.float64))
+    assert arr["word_bytes"].astype(np.uint8).tobytes() == b"".join(want.words)

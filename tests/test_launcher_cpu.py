@@ -144,3 +144,49 @@ def test_launcher_imports_no_engine():
     p = subprocess.run([sys.executable, "-c", code], cwd=ROOT, capture_output=True, text=True, timeout=60)
     assert p.returncode == 0, p.stderr
     assert p.stdout.split() == ["False", "False"]
+
+
+def test_full_and_dump_options_parse():
+    sys.path.insert(0, ROOT)
+    import bench
+
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.full is False and a.dump_outputs == "" and a.steps == 7 and a.warmup == 2
+    a = bench.parse(["--full", "--dump-outputs", "d"])
+    assert a.full is True and a.dump_outputs == "d"
+
+
+def test_dump_outputs_arrays_and_budget(tmp_path, monkeypatch):
+    """--dump-outputs: float arrays of the table; above the budget a fixed seeded sample of its rows."""
+    import numpy as np
+
+    sys.path.insert(0, ROOT)
+    import bench
+    from cuda_mapreduce_amd.ops import cpu_count_synth
+
+    res = cpu_count_synth(1 << 20, 0, 3, 2000, 1.0, long_frac=0.2)
+    info = bench.dump_outputs(res, str(tmp_path / "a"))
+    assert info["sampled"] is False and info["rows"] == info["of"] == len(res)
+    arr = {f[:-4]: np.load(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")}
+    assert sorted(arr) == ["counts", "first_offsets", "total", "word_bytes", "word_lengths"]
+    assert arr["word_bytes"].dtype == np.float32 and all(arr[k].dtype == np.float64 for k in arr if k != "word_bytes")
+    assert np.array_equal(arr["counts"], res.counts.astype(np.float64))
+    assert np.array_equal(arr["first_offsets"], res.first_off.astype(np.float64))
+    assert arr["word_bytes"].astype(np.uint8).tobytes() == b"".join(res.words)
+    assert arr["total"].tolist() == [float(res.total), float(len(res))]
+    assert info["bytes"] == sum(a.nbytes for a in arr.values())
+
+    budget = 20000
+    monkeypatch.setattr(bench, "DUMP_BUDGET", budget)
+    dumps = []
+    for name in ("b", "c"):
+        info = bench.dump_outputs(res, str(tmp_path / name))
+        assert info["sampled"] is True and 0 < info["rows"] < len(res) and info["bytes"] <= budget
+        dumps.append({f[:-4]: np.load(tmp_path / name / f) for f in os.listdir(tmp_path / name)})
+    b, c = dumps
+    assert sorted(b) == ["counts", "first_offsets", "rows", "total", "word_bytes", "word_lengths"]
+    assert all(np.array_equal(b[k], c[k]) for k in b)  # the same sample every time
+    rows = b["rows"].astype(np.int64)
+    assert len(rows) == info["rows"] and np.all(np.diff(rows) > 0)
+    assert np.array_equal(b["counts"], res.counts[rows].astype(np.float64))
+    assert b["word_bytes"].astype(np.uint8).tobytes() == b"".join(res.words[i] for i in rows)

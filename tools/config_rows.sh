@@ -3,18 +3,20 @@
 # (VERDICT r5 item 4): the headline, 64 GiB resident, the per-rank halves of both
 # 8-GPU configs at full size (256gb-8gpu with the merge forced on, shuffle and dense;
 # 1tb-8gpu-host-staged: 128 GiB over PCIe), then the ./wordcount file path.
-# -> gpurun_out/config_rows.txt (+ JSON per row under gpurun_out/cfg/)
+# -> $WC_OUT/config_rows.txt (+ JSON per row under $WC_OUT/cfg/)
 export TMPDIR=/tmp
-OUT=gpurun_out/cfg
+export WC_OUT=${WC_OUT:-out}  # where this script keeps its results
+mkdir -p "$WC_OUT"
+OUT=$WC_OUT/cfg
 mkdir -p $OUT
-R=gpurun_out/config_rows.txt
+R=$WC_OUT/config_rows.txt
 : > $R
 (while sleep 45; do echo "heartbeat $(date +%T)"; done) & HB=$!
 trap "kill $HB 2>/dev/null" EXIT
 row() {  # name, timeout, args...
   local name=$1 t=$2; shift 2
   echo "running $name" 
-  timeout -k 10 $t python3 bench.py "$@" > $OUT/$name.json 2> $OUT/$name.err || { echo "FAIL $name" | tee -a $R; tail -5 $OUT/$name.err; return 1; }
+  timeout -k 10 $t python3 bench.py --full "$@" > $OUT/$name.json 2> $OUT/$name.err || { echo "FAIL $name" | tee -a $R; tail -5 $OUT/$name.err; return 1; }
   python3 - "$OUT/$name.json" "$name" >> $R <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); st = d["stages"]

@@ -2,17 +2,19 @@
 # Merged-finalize tax at world size 1: bench.py plain vs
 # the RCCL merge protocol forced on (WC_MERGE_ALWAYS=1) for shuffle and dense,
 # interleaved REPS times (the planned merge runs from the second job on).
-#   tools/merge_tax.sh [bench args]   -> gpurun_out/merge_tax.txt
+#   tools/merge_tax.sh [bench args]   -> $WC_OUT/merge_tax.txt
 export TMPDIR=/tmp
+export WC_OUT=${WC_OUT:-out}  # where this script keeps its results
+mkdir -p "$WC_OUT"
 REPS=${REPS:-2}
-OUT=gpurun_out/merge_tax.txt
+OUT=$WC_OUT/merge_tax.txt
 : > $OUT
 for r in $(seq $REPS); do
   for m in plain shuffle dense; do
     if [ $m = plain ]; then
-      timeout -k 10 200 python3 bench.py --no-oracle --steps 200 --warmup 10 "$@" > /tmp/mt.json 2> /tmp/mt.err
+      timeout -k 10 200 python3 bench.py --full --no-oracle --steps 200 --warmup 10 "$@" > /tmp/mt.json 2> /tmp/mt.err
     else
-      WC_MERGE_ALWAYS=1 timeout -k 10 200 python3 bench.py --no-oracle --steps 200 --warmup 10 --merge $m "$@" \
+      WC_MERGE_ALWAYS=1 timeout -k 10 200 python3 bench.py --full --no-oracle --steps 200 --warmup 10 --merge $m "$@" \
         > /tmp/mt.json 2> /tmp/mt.err
     fi
     rc=$?
@@ -23,9 +25,10 @@ print('$m', d['ms_per_step'], d['value'], s['device_ms']['merge'], s.get('merges
   done
 done
 python3 - <<'PY'
+import os
 import collections, statistics
 rows = collections.defaultdict(list)
-for line in open("gpurun_out/merge_tax.txt"):
+for line in open(os.environ["WC_OUT"] + "/merge_tax.txt"):
     m, ms, gbs, mg, pl, rd = line.split()
     rows[m].append((float(ms), float(gbs), float(mg), int(pl), int(rd)))
 base = statistics.median(r[0] for r in rows["plain"])

@@ -3,11 +3,13 @@
 # vocabulary sweep, LONG-word load, 64 GiB config (hot-table reuse A/B), the per-rank
 # halves of both 8-GPU configs at full size, merge forced at world 1, kernel trace.
 export TMPDIR=/tmp
-OUT=gpurun_out/r3s
+export WC_OUT=${WC_OUT:-out}  # where this script keeps its results
+mkdir -p "$WC_OUT"
+OUT=$WC_OUT/r3s
 mkdir -p $OUT
 run() {  # name, timeout, args...
   local name=$1 t=$2; shift 2
-  timeout -k 10 $t python bench.py "$@" > $OUT/$name.json 2> $OUT/$name.err || { echo "FAIL $name"; tail -5 $OUT/$name.err; return 1; }
+  timeout -k 10 $t python bench.py --full "$@" > $OUT/$name.json 2> $OUT/$name.err || { echo "FAIL $name"; tail -5 $OUT/$name.err; return 1; }
   python3 -c "import json,sys; d=json.loads(open('$OUT/$name.json').read().strip().splitlines()[-1]); st=d['stages']; print('%-28s %8.1f GB/s %8.4f ms/step valid=%s keys=%s dev=%s' % ('$name', d['value'], d['ms_per_step'], d['validated'], d['distinct_words'], st['device_ms']))"
 }
 if [ $# -gt 0 ]; then  # only the named rows

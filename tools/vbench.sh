@@ -4,24 +4,27 @@
 # 50 timed steps each; prints every run and the median per build.
 # tools/vbench.sh [bench args]   (REPS=3 by default)
 export TMPDIR=/tmp
+export WC_OUT=${WC_OUT:-out}  # where this script keeps its results
+mkdir -p "$WC_OUT"
 REPS=${REPS:-3}
 libs="cuda_mapreduce_amd/lib/libwc.so $(ls cuda_mapreduce_amd/lib/variants/*.so 2>/dev/null)"
-: > gpurun_out/vb_all.txt
+: > $WC_OUT/vb_all.txt
 for r in $(seq $REPS); do
   for so in $libs; do
     n=$(basename $so .so)
-    WC_LIB=$PWD/$so timeout -k 10 150 python3 bench.py --no-oracle --steps 50 --warmup 10 "$@" > gpurun_out/vb_$n.json 2> gpurun_out/vb_$n.err
+    WC_LIB=$PWD/$so timeout -k 10 150 python3 bench.py --full --no-oracle --steps 50 --warmup 10 "$@" > $WC_OUT/vb_$n.json 2> $WC_OUT/vb_$n.err
     rc=$?
-    if [ $rc -ne 0 ] && [ $rc -ne 1 ]; then echo "FAILED $so rc=$rc"; tail -3 gpurun_out/vb_$n.err; exit 1; fi
+    if [ $rc -ne 0 ] && [ $rc -ne 1 ]; then echo "FAILED $so rc=$rc"; tail -3 $WC_OUT/vb_$n.err; exit 1; fi
     python3 -c "
-import json; d=[json.loads(l) for l in open('gpurun_out/vb_$n.json') if l.startswith('{')][-1]
-print('$n', d['value'])" >> gpurun_out/vb_all.txt
+import json; d=[json.loads(l) for l in open('$WC_OUT/vb_$n.json') if l.startswith('{')][-1]
+print('$n', d['value'])" >> $WC_OUT/vb_all.txt
   done
 done
 python3 - "$*" <<'PY'
+import os
 import collections, statistics, sys
 runs = collections.defaultdict(list)
-for line in open("gpurun_out/vb_all.txt"):
+for line in open(os.environ["WC_OUT"] + "/vb_all.txt"):
     n, v = line.split()
     runs[n].append(float(v))
 for n, v in runs.items():
