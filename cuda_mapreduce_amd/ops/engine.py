@@ -362,7 +362,7 @@ def virtual_bench(ranks: int, nbytes: int, seed: int = 1, vocab: int = 100000, z
 
 
 def loopback_count(data: bytes, ranks: int, devices: Optional[Sequence[int]] = None, all_ranks: bool = False,
-                   resident: bool = False, warm: Optional[bytes] = None, **opts) -> Result:
+                   resident: bool = False, warm: Optional[bytes] = None, global_base: int = 0, **opts) -> Result:
     """`ranks` virtual ranks (threads) on `devices` count shards and merge in-process.
 
     Returns rank 0's table; with ``all_ranks`` every rank receives the merged
@@ -370,11 +370,12 @@ def loopback_count(data: bytes, ranks: int, devices: Optional[Sequence[int]] = N
     ``resident`` each shard is counted from HBM and the merge runs behind the
     pending last pass (the bench's speculative merged finalize).  ``warm``: a
     first job on that text (its result dropped), so the merge of ``data``
-    plans from the caps it learned."""
+    plans from the caps it learned.  ``global_base``: the text's offset in the
+    job; each shard is counted at ``global_base`` + its begin."""
     ptr, keep = _u8ptr(data)
     wptr, wkeep = _u8ptr(warm) if warm is not None else (None, b"")
     devs = (ctypes.c_int * ranks)(*(devices if devices is not None else [0] * ranks))
     o = default_options(**opts)
     return Result._from_native(
-        check_ptr(lib.wc_loopback_count(ptr, len(keep), ranks, devs, ctypes.byref(o), int(all_ranks), int(resident),
-                                        wptr, len(wkeep))))
+        check_ptr(lib.wc_loopback_count_at(ptr, len(keep), ranks, devs, ctypes.byref(o), int(all_ranks),
+                                           int(resident), wptr, len(wkeep), global_base)))

@@ -128,6 +128,11 @@ wc_result* wc_loopback_count(const uint8_t* text, uint64_t n, int ranks, const i
                              int all_ranks, int resident, const uint8_t* warm, uint64_t warm_n);
 /* warm (nullable): every rank first runs a job on its shard of `warm` (the merge
  * learns its caps there), then the job on `text` — a planned merge. */
+/* The same with the text placed at `global_base` of the job: each shard is
+ * counted at global_base + its begin, so first offsets come back absolute. */
+wc_result* wc_loopback_count_at(const uint8_t* text, uint64_t n, int ranks, const int* devices, const wc_options* o,
+                                int all_ranks, int resident, const uint8_t* warm, uint64_t warm_n,
+                                uint64_t global_base);
 
 #ifdef __cplusplus
 }

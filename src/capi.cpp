@@ -828,6 +828,12 @@ wc_result* wc_virtual_bench(const wc_options* o, int ranks, int device, uint64_t
 
 wc_result* wc_loopback_count(const uint8_t* text, uint64_t n, int ranks, const int* devices, const wc_options* o,
                              int all_ranks, int resident, const uint8_t* warm, uint64_t warm_n) {
+  return wc_loopback_count_at(text, n, ranks, devices, o, all_ranks, resident, warm, warm_n, 0);
+}
+
+wc_result* wc_loopback_count_at(const uint8_t* text, uint64_t n, int ranks, const int* devices, const wc_options* o,
+                                int all_ranks, int resident, const uint8_t* warm, uint64_t warm_n,
+                                uint64_t global_base) {
   wc_result* out = new wc_result;
   std::vector<std::string> errs(ranks);
   std::vector<wc::KeyTable> tables(ranks);
@@ -859,9 +865,9 @@ wc_result* wc_loopback_count(const uint8_t* text, uint64_t n, int ranks, const i
             WC_HIP_CHECK(hipSetDevice(opt.device));
             wc::dev_malloc(&d, len + 64);
             WC_HIP_CHECK(hipMemcpy(d, tx + sr.begin, len, hipMemcpyHostToDevice));
-            eng.count_device(d, len, len, sr.begin, sr.begin ? tx[sr.begin - 1] : ' ');
+            eng.count_device(d, len, len, global_base + sr.begin, sr.begin ? tx[sr.begin - 1] : ' ');
           } else if (sr.end > sr.begin) {
-            eng.count_host(tx + sr.begin, sr.end - sr.begin, sr.begin);
+            eng.count_host(tx + sr.begin, sr.end - sr.begin, global_base + sr.begin);
           }
           wc::KeyTable kt = eng.result(comms[r].get(), all_ranks != 0);
           if (d) (void)hipFree(d);

@@ -39,3 +39,26 @@ def test_engine_matches_python_definition(text, reps):
     got = e.result()
     want = py_count(text)
     assert [(w, int(c)) for w, c in zip(got.words, got.counts)] == want
+
+
+any_piece = st.one_of(
+    st.binary(max_size=300),                                                       # any bytes, delimiters among them
+    st.tuples(st.integers(1, 40), st.sampled_from([b" ", b"\n", b"\r", b"\r\n"])).map(lambda t: t[1] * t[0]),  # delimiter runs
+    st.tuples(st.integers(0, 255), st.integers(1, 70)).map(lambda t: bytes([t[0]]) * t[1]),  # one byte repeated (NUL, 0xFF ...)
+)
+
+
+@settings(max_examples=40, deadline=None, suppress_health_check=[HealthCheck.too_slow])
+@given(st.lists(any_piece, max_size=200).map(b"".join), st.integers(0, 3))
+def test_engine_matches_python_definition_all_bytes(text, reps):
+    """The same over all 256 byte values: arbitrary binary pieces, delimiter runs
+    and runs of one arbitrary byte up to 70 long (all-NUL and all-0xFF words of
+    every key class, past the hot table's 64-byte limit)."""
+    text = text * (1 + reps * 40)
+    e = engine()
+    e.reset()
+    e.count_bytes(text)
+    got = e.result()
+    want = py_count(text)
+    assert [(w, int(c)) for w, c in zip(got.words, got.counts)] == want
+    assert got.total == sum(c for _, c in want)
