@@ -57,6 +57,7 @@ def _load() -> ctypes.CDLL:
         "wc_debug_read_file": (c_int, [c_char_p, c_uint64, c_uint64, c_uint64, P8, POINTER(c_uint64)]),
         "wc_debug_order": (c_int, [c_int, c_int, P64, c_uint64, c_int, P64, POINTER(ctypes.c_uint32),
                                    POINTER(c_int), POINTER(ctypes.c_double), P64]),
+        "wc_debug_top_k": (c_int, [c_int, P64, c_uint64, c_uint64, POINTER(ctypes.c_uint32), P64, P64]),
         "wc_default_options": (None, [POINTER(Options)]),
         "wc_engine_create": (c_void_p, [POINTER(Options)]),
         "wc_engine_destroy": (None, [c_void_p]),
@@ -74,6 +75,7 @@ def _load() -> ctypes.CDLL:
         "wc_count_resident": (c_int, [c_void_p, c_uint64, c_uint64]),
         "wc_finalize_device": (c_int, [c_void_p, c_void_p, P64]),
         "wc_engine_result": (c_void_p, [c_void_p, c_void_p, c_int]),
+        "wc_engine_top_k": (c_void_p, [c_void_p, c_void_p, c_int, c_uint64]),
         "wc_engine_stats_json": (c_int, [c_void_p, c_char_p, c_int]),
         "wc_engine_sync": (c_int, [c_void_p]),
         "wc_result_size": (c_uint64, [c_void_p]),

@@ -42,6 +42,15 @@ class Result:
     def rows(self):
         return list(zip(self.words, (int(c) for c in self.counts)))
 
+    def top(self, k: int) -> "Result":
+        """The min(k, len) most frequent rows, by (count descending, row position
+        ascending), in that order; ``total`` stays the whole table's.  Pure
+        Python on the host: the oracle of ``Engine.top_k``."""
+        order = sorted(range(len(self)), key=lambda i: (-int(self.counts[i]), i))[:max(int(k), 0)]
+        idx = np.asarray(order, dtype=np.int64)
+        return Result([self.words[i] for i in order], np.asarray(self.counts, np.uint64)[idx],
+                      np.asarray(self.first_off, np.uint64)[idx], self.total)
+
     @classmethod
     def _from_native(cls, p) -> "Result":
         try:
@@ -229,6 +238,13 @@ class Engine:
     def result(self, comm: Optional[Comm] = None, all_ranks: bool = False) -> Result:
         return Result._from_native(check_ptr(lib.wc_engine_result(self._p, comm._p if comm else None, int(all_ranks))))
 
+    def top_k(self, k: int, comm: Optional[Comm] = None, all_ranks: bool = False) -> Result:
+        """Finalize as ``result`` does, then select the ``min(k, keys)`` most frequent
+        rows on the GPU — (count descending, first occurrence ascending), in that
+        order — and copy only those to the host.  ``total`` is the whole table's."""
+        return Result._from_native(check_ptr(lib.wc_engine_top_k(self._p, comm._p if comm else None, int(all_ranks),
+                                                                 int(k))))
+
     def sync(self) -> None:
         """hipDeviceSynchronize on the engine's device (the bench's timing brackets)."""
         check(lib.wc_engine_sync(self._p))
@@ -330,6 +346,18 @@ def file_read_bench(path: str, piece: int = 64 << 20, device: int = 0):
     g, n = ctypes.c_double(0), ctypes.c_uint64(0)
     check(lib.wc_file_read_bench(path.encode(), piece, device, ctypes.byref(g), ctypes.byref(n)))
     return g.value, n.value
+
+
+def debug_top_k(counts: np.ndarray, k: int, device: int = 0):
+    """Kernel test hook (src/kernels/topk.hip steps 1-3) on a count column whose row
+    order is the tie-break -> (the min(k, n) selected rows in final order, the column sum)."""
+    c = np.ascontiguousarray(counts, dtype=np.uint64)
+    rows = np.zeros(max(min(int(k), len(c)), 1), np.uint32)
+    n_out, total = ctypes.c_uint64(0), ctypes.c_uint64(0)
+    check(lib.wc_debug_top_k(device, c.ctypes.data_as(_P64), len(c), int(k),
+                             rows.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), ctypes.byref(n_out),
+                             ctypes.byref(total)))
+    return rows[:int(n_out.value)], int(total.value)
 
 
 def shard_range(data: bytes, rank: int, world: int):

@@ -44,6 +44,11 @@ int wc_debug_first_order(int device, const uint64_t* keys, uint64_t n, int reps,
  * nonzero bitmap words left afterwards (0: the bitmap was cleared). */
 int wc_debug_order(int device, int method, const uint64_t* keys, uint64_t n, int reps, uint64_t* sorted,
                    uint32_t* perm, int* overflow, double* ms, uint64_t* residue);
+/* Kernel test hook: top-K selection on a count column of n rows (row order is
+ * the tie-break): rows[0, *n_out) = the min(k, n) rows first under (count
+ * descending, row ascending), in that order; *sum = the column's sum. */
+int wc_debug_top_k(int device, const uint64_t* counts, uint64_t n, uint64_t k, uint32_t* rows, uint64_t* n_out,
+                   uint64_t* sum);
 void wc_default_options(wc_options* o);
 
 wc_engine* wc_engine_create(const wc_options* o);
@@ -82,6 +87,10 @@ int wc_synth_device(wc_engine* e, uint64_t n, uint64_t first_segment, uint64_t s
 int wc_count_resident(wc_engine* e, uint64_t n, uint64_t global_base);
 int wc_finalize_device(wc_engine* e, wc_comm* comm, uint64_t* n_keys);
 wc_result* wc_engine_result(wc_engine* e, wc_comm* comm, int all_ranks);
+/* The same finalize, then the min(k, keys) most frequent rows selected on the
+ * device, in (count descending, first occurrence ascending) order; the result's
+ * total (wc_result_total) is the whole table's. */
+wc_result* wc_engine_top_k(wc_engine* e, wc_comm* comm, int all_ranks, uint64_t k);
 /* JSON object with the engine's Stats. Returns required length. */
 int wc_engine_stats_json(wc_engine* e, char* buf, int cap);
 int wc_engine_sync(wc_engine* e);

@@ -50,6 +50,10 @@ struct Stats {
   // in the gather.
   uint32_t merge_collectives = 0;
   uint64_t merge_sent_bytes = 0, merge_peer_bytes = 0, merge_root_recv_bytes = 0;
+  // Output stage: bytes the last result() / top_k() copied to the host, and
+  // the host wall clock of the last top_k()'s selection (after its finalize).
+  uint64_t download_bytes = 0;
+  double host_topk_ms = 0;
   // Host wall clock of the last job's API calls (count_*, finalize / result).
   double host_count_ms = 0, host_finalize_ms = 0;
   // Device time of the last job's stages, from events on the engine stream
@@ -149,6 +153,17 @@ class Engine {
   // Merge with other ranks (comm may be null), order by first occurrence and
   // download.  Only rank 0 receives rows unless all_ranks.
   KeyTable result(Comm* comm = nullptr, bool all_ranks = false);
+
+  // The same finalize, then the min(k, keys) most frequent rows selected on
+  // the device — (count descending, first occurrence ascending), in that
+  // order — so only k rows and their words are copied to the host.  `total`
+  // is the whole table's; *n_keys (optional) its key count.  k = 0: no rows.
+  // result() or another top_k() may follow: the device table stays intact.
+  KeyTable top_k(uint64_t k, Comm* comm = nullptr, bool all_ranks = false, uint64_t* n_keys = nullptr);
+  // Rows of the table the last finalize_device() left on this device, without
+  // finalizing again: the `top` most frequent when 0 < top < keys (as top_k),
+  // else every row in first-occurrence order (as result()).
+  KeyTable finalized_rows(uint64_t top = 0);
 
   // Device-side finalisation only (no download): returns distinct keys.  Used
   // by the benchmark to time the full pipeline to an ordered device table.

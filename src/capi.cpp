@@ -379,6 +379,51 @@ int wc_debug_first_order(int device, const uint64_t* keys, uint64_t n, int reps,
   return wc_debug_order(device, 0, keys, n, reps, sorted, perm, overflow, ms, &residue);
 }
 
+// Top-K selection (kernels/topk.hip steps 1-3) on a given count column, row
+// order the tie-break: rows[0, *n_out) = the min(k, n) rows first under (count
+// descending, row ascending), in that order; *sum = the column's sum.
+int wc_debug_top_k(int device, const uint64_t* counts, uint64_t n, uint64_t k, uint32_t* rows, uint64_t* n_out,
+                   uint64_t* sum) {
+  return guard([&] {
+    WC_HIP_CHECK(hipSetDevice(device));
+    hipStream_t s = nullptr;
+    const uint64_t m = std::min(k, n);
+    const size_t nn = n ? n : 1, mm = m ? m : 1;
+    const size_t sel_ws = wc::topk_select_ws_bytes(n), ord_ws = wc::topk_order_ws_bytes(m);
+    uint8_t* mem = nullptr;
+    wc::dev_malloc(&mem, nn * 8 + mm * 4 + sel_ws + ord_ws + 8 * 256);
+    uint8_t* p = mem;
+    auto take = [&](size_t b) {
+      uint8_t* r = p;
+      p += (b + 255) / 256 * 256;
+      return r;
+    };
+    uint64_t* cnt = reinterpret_cast<uint64_t*>(take(nn * 8));
+    wc::TopkState* st = reinterpret_cast<wc::TopkState*>(take(sizeof(wc::TopkState)));
+    unsigned long long* err = reinterpret_cast<unsigned long long*>(take(8));
+    uint32_t* sel = reinterpret_cast<uint32_t*>(take(mm * 4));
+    void* ws = take(sel_ws);
+    void* ows = take(ord_ws);
+    WC_HIP_CHECK(hipMemcpy(cnt, counts, n * 8, hipMemcpyHostToDevice));
+    WC_HIP_CHECK(hipMemset(err, 0, 8));
+    wc::topk_select(cnt, nullptr, nullptr, n, m, ws, st, sel, s, wc::Bounds{err, m});
+    wc::TopkState hs;
+    WC_HIP_CHECK(hipMemcpy(&hs, st, sizeof hs, hipMemcpyDeviceToHost));
+    if (m) {
+      WC_CHECK(hs.rem_bits == 0 && hs.n_gt + hs.k_rem == m, "top_k: inconsistent selection state");
+      const uint32_t* ord = wc::topk_order(cnt, n, sel, m, (int)hs.max_bits, ows, s, wc::Bounds{err, m});
+      WC_HIP_CHECK(hipMemcpy(rows, ord, m * 4, hipMemcpyDeviceToHost));
+    }
+    unsigned long long bw = 0;
+    WC_HIP_CHECK(hipMemcpy(&bw, err, 8, hipMemcpyDeviceToHost));
+    WC_HIP_CHECK(hipFree(mem));
+    WC_CHECK(bw == 0, std::string("bounds guard: ") + wc::bounds_kernel_name((uint32_t)(bw >> 56)) + " reached row " +
+                          std::to_string(bw & ((1ull << 56) - 1)) + " past its buffer");
+    *n_out = m;
+    *sum = hs.sum;
+  });
+}
+
 int wc_device_count(void) {
   int n = 0;
   if (hipGetDeviceCount(&n) != hipSuccess) return 0;
@@ -501,6 +546,15 @@ wc_result* wc_engine_result(wc_engine* e, wc_comm* c, int all_ranks) {
   return r;
 }
 
+wc_result* wc_engine_top_k(wc_engine* e, wc_comm* c, int all_ranks, uint64_t k) {
+  wc_result* r = new wc_result;
+  if (guard([&] { r->t = e->e->top_k(k, c ? c->c.get() : nullptr, all_ranks != 0); }) != 0) {
+    delete r;
+    return nullptr;
+  }
+  return r;
+}
+
 int wc_engine_stats_json(wc_engine* e, char* buf, int cap) {
   const wc::Stats& s = e->e->stats();
   char tmp[2048];
@@ -508,17 +562,17 @@ int wc_engine_stats_json(wc_engine* e, char* buf, int cap) {
                          "{\"bytes\": %llu, \"tokens\": %llu, \"keys\": %llu, \"records\": %llu, "
                          "\"long_tokens\": %llu, \"long_direct\": %u, \"chunks\": %u, "
                          "\"map_reruns\": %u, \"table_splits\": %u, \"log2_buckets\": %u, \"order_path\": %u, "
-                         "\"merges_planned\": %u, \"merge_redos\": %u, "
+                         "\"merges_planned\": %u, \"merge_redos\": %u, \"download_bytes\": %llu, "
                          "\"device_ms\": {\"map\": %.4f, \"reduce\": %.4f, \"finalize\": %.4f, \"merge\": %.4f, "
                          "\"idle\": %.4f, \"total\": %.4f}, "
-                         "\"host_ms\": {\"count\": %.4f, \"finalize\": %.4f}}",
+                         "\"host_ms\": {\"count\": %.4f, \"finalize\": %.4f, \"top_k\": %.4f}}",
                          (unsigned long long)s.bytes, (unsigned long long)s.tokens, (unsigned long long)s.keys,
                          (unsigned long long)s.records, (unsigned long long)s.long_tokens, s.long_direct, s.chunks,
                          s.map_reruns, s.table_splits, s.log2_buckets, s.order_path,
-                         s.merges_planned, s.merge_redos,
+                         s.merges_planned, s.merge_redos, (unsigned long long)s.download_bytes,
                          s.map_ms,
                          s.reduce_ms, s.finalize_ms, s.merge_ms, s.idle_ms, s.device_ms, s.host_count_ms,
-                         s.host_finalize_ms);
+                         s.host_finalize_ms, s.host_topk_ms);
   if (buf && cap > 0) {
     std::strncpy(buf, tmp, (size_t)cap - 1);
     buf[cap - 1] = 0;

@@ -1112,6 +1112,7 @@ KeyTable Engine::Impl::download_cols() {
   if (!arena.empty())
     WC_HIP_CHECK(hipMemcpyAsync(arena.data(), cols_arena, arena.size(), hipMemcpyDeviceToHost, s));
   WC_HIP_CHECK(hipStreamSynchronize(s));
+  st.download_bytes = n * (5 * 8 + 4) + arena.size();
   KeyTable t;
   t.words.resize(n);
   t.counts = std::move(cnt);
@@ -1127,6 +1128,107 @@ KeyTable Engine::Impl::download_cols() {
     }
     t.total += t.counts[i];
   }
+  return t;
+}
+
+// The min(k, n) most frequent rows of the finalized columns, selected, ordered
+// and gathered on the device (kernels/topk.hip).  Two host waits: the
+// selection's state (the column sum, the largest count's bit length, the bytes
+// of the selected words) and the download of the k rows + their words; the
+// bytes copied do not depend on n.  m <= TOPK_SMALL rows are ordered by one
+// block in LDS, more by the radix sort on ~count.
+KeyTable Engine::Impl::select_top(uint64_t k) {
+  Range r("wc_topk");
+  const double t0 = now_seconds();
+  WC_HIP_CHECK(hipSetDevice(dev));
+  WC_CHECK(cols.dn == nullptr && cols.occ == nullptr, "top_k needs finalized columns");
+  const uint64_t n = cols.n, m = std::min(k, n), mm = m ? m : 1;
+  auto stage = [&](const char* what) {  // WC_SYNC_DEBUG: attribute a device fault to a stage
+    if (!sync_debug) return;
+    const hipError_t e = hipStreamSynchronize(s);
+    fprintf(stderr, "[wc] top_k  %s n=%llu k=%llu -> %s\n", what, (unsigned long long)n, (unsigned long long)m,
+            hipGetErrorString(e));
+  };
+  DeviceArena& A = topk_mem;
+  const size_t sel_ws = topk_select_ws_bytes(n), ord_ws = topk_order_ws_bytes(m);
+  A.reset();
+  A.reserve(sel_ws + ord_ws + mm * (6 * 8 + 2 * 4) + 16 * 256);
+  TopkState* d_st = A.take_n<TopkState>(1);
+  void* ws = A.take(sel_ws);
+  uint32_t* sel = A.take_n<uint32_t>(mm);
+  topk_select(cols.cnt, cols.k1, cols.sref_len, n, m, ws, d_st, sel, s, bounds(m));
+  stage("select");
+  h_topk_st.resize(128);
+  WC_HIP_CHECK(hipMemcpyAsync(h_topk_st.data(), d_st, sizeof(TopkState), hipMemcpyDeviceToHost, s));
+  WC_HIP_CHECK(hipMemcpyAsync(h_topk_st.data() + 64, d_bounds, 8, hipMemcpyDeviceToHost, s));
+  WC_HIP_CHECK(hipStreamSynchronize(s));  // wait 1
+  TopkState hs;
+  uint64_t bw = 0;
+  std::memcpy(&hs, h_topk_st.data(), sizeof hs);
+  std::memcpy(&bw, h_topk_st.data() + 64, 8);
+  check_bounds(bw, "top_k's selection");
+  KeyTable t;
+  t.total = hs.sum;
+  st.download_bytes = sizeof(TopkState) + 8;
+  if (m) {
+    WC_CHECK(hs.rem_bits == 0 && hs.n_gt + hs.k_rem == m && hs.blob_bytes <= cols_arena_bytes,
+             "top_k: inconsistent selection state");
+    const uint32_t* rows = topk_order(cols.cnt, n, sel, m, (int)hs.max_bits, A.take(ord_ws), s, bounds(m));
+    stage("order");
+    TopkDst d{};
+    d.k0 = A.take_n<uint64_t>(m);
+    d.k1 = A.take_n<uint64_t>(m);
+    d.cnt = A.take_n<uint64_t>(m);
+    d.first = A.take_n<uint64_t>(m);
+    d.src = A.take_n<uint64_t>(m);
+    d.off = A.take_n<uint64_t>(m);
+    d.len = A.take_n<uint32_t>(m);
+    topk_gather(TopkSrc{cols.k0, cols.k1, cols.cnt, cols.first, cols.sref_off, cols.sref_len, n}, rows, m, d, s,
+                bounds(m));
+    stage("gather");
+    const uint64_t nb = hs.blob_bytes;
+    uint8_t* blob = nullptr;
+    if (nb) {
+      topk_blob.reset();
+      topk_blob.reserve(nb + 256);
+      blob = topk_blob.take_n<uint8_t>(nb);
+      topk_words(cols_arena, cols_arena_bytes, d, m, blob, nb, d_bounds, s);
+      stage("words");
+    }
+    // k0 | k1 | cnt | first | off [m u64 each] | len [m u32] | bounds word | blob
+    const size_t o_len = 5 * m * 8, o_bw = (o_len + m * 4 + 7) / 8 * 8, o_blob = o_bw + 8;
+    h_topk.resize(o_blob + nb);
+    uint8_t* h = h_topk.data();
+    const uint64_t* colsrc[5] = {d.k0, d.k1, d.cnt, d.first, d.off};
+    for (int c = 0; c < 5; ++c)
+      WC_HIP_CHECK(hipMemcpyAsync(h + (size_t)c * m * 8, colsrc[c], m * 8, hipMemcpyDeviceToHost, s));
+    WC_HIP_CHECK(hipMemcpyAsync(h + o_len, d.len, m * 4, hipMemcpyDeviceToHost, s));
+    WC_HIP_CHECK(hipMemcpyAsync(h + o_bw, d_bounds, 8, hipMemcpyDeviceToHost, s));
+    if (nb) WC_HIP_CHECK(hipMemcpyAsync(h + o_blob, blob, nb, hipMemcpyDeviceToHost, s));
+    WC_HIP_CHECK(hipStreamSynchronize(s));  // wait 2
+    std::memcpy(&bw, h + o_bw, 8);
+    check_bounds(bw, "top_k's gather");
+    st.download_bytes += m * (5 * 8 + 4) + 8 + nb;
+    const uint64_t* hk0 = reinterpret_cast<const uint64_t*>(h);
+    const uint64_t *hk1 = hk0 + m, *hcnt = hk1 + m, *hfirst = hcnt + m, *hoff = hfirst + m;
+    const uint32_t* hlen = reinterpret_cast<const uint32_t*>(h + o_len);
+    t.words.resize(m);
+    t.counts.assign(hcnt, hcnt + m);
+    t.first_off.assign(hfirst, hfirst + m);
+    for (uint64_t i = 0; i < m; ++i) {
+      if (!key_is_hashed(hk1[i])) {
+        uint8_t w[KEY_INLINE_MAX];
+        const uint32_t len = inline_bytes(hk0[i], hk1[i], w);
+        t.words[i].assign(reinterpret_cast<const char*>(w), len);
+      } else {
+        WC_CHECK(hoff[i] + hlen[i] <= nb, "top_k: word reference outside the blob");
+        t.words[i].assign(reinterpret_cast<const char*>(h + o_blob) + hoff[i], hlen[i]);
+      }
+    }
+  }
+  st.host_topk_ms = (now_seconds() - t0) * 1e3;
+  WC_LOG(LOG_INFO, "dev %d: top_k %.3f ms (host), k %llu of %llu keys, %llu bytes to the host", dev, st.host_topk_ms,
+         (unsigned long long)k, (unsigned long long)n, (unsigned long long)st.download_bytes);
   return t;
 }
 
@@ -1603,6 +1705,24 @@ KeyTable Engine::result(Comm* comm, bool all_ranks) {
     return t;
   }
   return im.download_cols();
+}
+
+KeyTable Engine::top_k(uint64_t k, Comm* comm, bool all_ranks, uint64_t* n_keys) {
+  Impl& im = *p_;
+  im.finalize(comm, all_ranks);
+  if (comm && comm->size() > 1 && comm->rank() != 0 && !all_ranks) {
+    if (n_keys) *n_keys = 0;
+    KeyTable t;
+    return t;
+  }
+  if (n_keys) *n_keys = im.cols.n;
+  return im.select_top(k);
+}
+
+KeyTable Engine::finalized_rows(uint64_t top) {
+  Impl& im = *p_;
+  WC_HIP_CHECK(hipSetDevice(im.dev));
+  return top && top < im.cols.n ? im.select_top(top) : im.download_cols();
 }
 
 }  // namespace wc

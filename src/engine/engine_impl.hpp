@@ -323,6 +323,14 @@ struct Engine::Impl {
   KeyCols cols_unsorted;       // its input, kept for a radix redo
   bool order_redo = false;     // the speculative finalize's sample sort overflowed (Stats::order_path 4)
   KeyTable download_cols();
+  // Top-K selection on the finalized columns (kernels/topk.hip): its own
+  // workspace, grown on demand and kept across calls — cols and the arena are
+  // only read, so result() and another top_k() may follow.
+  DeviceArena topk_mem;    // state, histogram, tile counts, selected rows, order workspace, compact columns
+  DeviceArena topk_blob;   // the selected rows' arena words (sized after the selection's host read)
+  PinnedBuffer h_topk_st;  // TopkState + the bounds word
+  PinnedBuffer h_topk;     // the K rows and their words
+  KeyTable select_top(uint64_t k);
 };
 
 // Multi-rank merge (dist/merge.cpp): replaces im.cols / cols_arena with the

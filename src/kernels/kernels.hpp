@@ -6,6 +6,7 @@
 //   wc_table_split    running table B -> 2B buckets (grows with the vocabulary)
 //   wc_table_compact  running table -> dense key list
 //   wc_radix_*        LSD radix sort (first-occurrence order, merge dictionary)
+//   wc_topk_*         the K most frequent rows of the ordered table (Engine::top_k)
 //   wc_synth_text     device-side synthetic text generator
 // Reference counterparts: mapKernel (/root/reference/main.cu:109-117) and the
 // single-thread reduceKernel (main.cu:119-123).
@@ -281,6 +282,10 @@ enum BoundsKernel : uint32_t {
   BND_TABLE_KEYS,    // reduce.hip wc_table_keys: (first, slot) rows
   BND_GATHER_TABLE,  // reduce.hip wc_gather_table: output rows and table slots
   BND_COMPACT,       // reduce.hip wc_table_compact: output rows
+  BND_TOPK_WRITE,    // topk.hip wc_topk_write: selected row indices
+  BND_TOPK_RANK,     // topk.hip wc_topk_rank: ordered row indices
+  BND_TOPK_GATHER,   // topk.hip wc_topk_gather: output rows and table rows
+  BND_TOPK_WORDS,    // topk.hip wc_topk_words: blob bytes and arena bytes
   BND_KERNELS
 };
 struct Bounds {
@@ -388,6 +393,52 @@ void launch_gather_cols(const uint64_t* k0, const uint64_t* k1, const uint64_t* 
                         uint64_t* ocnt, uint64_t* ofirst, uint64_t* osoff, uint32_t* oslen, uint64_t n, hipStream_t s,
                         const uint64_t* dn = nullptr, const Bounds& bnd = {});
 void launch_iota_u32(uint32_t* v, uint64_t n, hipStream_t s);
+
+// ---- top-K selection (topk.hip): the K most frequent rows of ordered columns ----
+// Rows first under (count descending, row ascending); every launch is
+// stream-ordered.  The host reads TopkState once, after topk_select: it sizes
+// the order (max_bits) and the blob of the selected rows' arena words.
+struct TopkState {  // 64 bytes, zeroed by topk_select
+  unsigned long long sum;         // the whole count column
+  unsigned long long thresh;      // T, the k-th largest count (while rem_bits > 0: its fixed high bits)
+  unsigned long long n_gt;        // rows with count > T
+  unsigned long long k_rem;       // rows with count == T taken (the first k - n_gt in row order)
+  unsigned long long rem_bits;    // low bits of T still open (0 after the select)
+  unsigned long long max_bits;    // bit length of the largest count
+  unsigned long long blob_bytes;  // arena bytes of the selected rows' words (k1 given)
+  unsigned long long pad;
+};
+constexpr uint32_t TOPK_SMALL = 2048;  // the order of up to this many rows: one block in LDS; above: the radix sort
+// Steps 1 + 2: sel[0, min(k, n)) = the selected rows in ascending row order
+// (k <= n < 2^32; bnd.cap = sel's rows).  k = 0: the sum alone.  k1 / slen
+// (nullable): the key columns, for TopkState::blob_bytes.  ws:
+// topk_select_ws_bytes(n) bytes.
+size_t topk_select_ws_bytes(uint64_t n);
+void topk_select(const uint64_t* cnt, const uint64_t* k1, const uint32_t* slen, uint64_t n, uint64_t k, void* ws,
+                 TopkState* st, uint32_t* sel, hipStream_t s, const Bounds& bnd = {});
+// Step 3: the m selected rows (of n) by descending count, ties in selection order;
+// bits >= TopkState::max_bits.  Returns the ordered rows (inside ws,
+// topk_order_ws_bytes(m) bytes).
+size_t topk_order_ws_bytes(uint64_t m);
+const uint32_t* topk_order(const uint64_t* cnt, uint64_t n, const uint32_t* sel, uint64_t m, int bits, void* ws,
+                           hipStream_t s, const Bounds& bnd = {});
+// Step 4: the rows' columns into dst (bnd.cap = its rows); len = the bytes of
+// a hashed key's word (0: inline key), src their arena offset, off their
+// offset in the blob (the rewritten sref_off); then the words' bytes into the
+// blob (errors into *err, nullable).
+struct TopkSrc {
+  const uint64_t *k0, *k1, *cnt, *first, *soff;
+  const uint32_t* slen;
+  uint64_t n;
+};
+struct TopkDst {
+  uint64_t *k0, *k1, *cnt, *first, *src, *off;
+  uint32_t* len;
+};
+void topk_gather(const TopkSrc& src, const uint32_t* rows, uint64_t m, const TopkDst& dst, hipStream_t s,
+                 const Bounds& bnd = {});
+void topk_words(const uint8_t* arena, uint64_t arena_bytes, const TopkDst& dst, uint64_t m, uint8_t* blob,
+                uint64_t blob_bytes, unsigned long long* err, hipStream_t s);
 
 // util.hip: fill several device regions (+ a few small copies, e.g. host words
 // from page-locked memory into device buffers) / copy several small device

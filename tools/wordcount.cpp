@@ -35,7 +35,8 @@ const char* kUsage =
     "  --compat=reference      CPU emulation of the reference program's quirks\n"
     "  --echo | --no-echo      echo the input after 'Input Data:' (default: echo)\n"
     "  --no-list               do not print per-word rows\n"
-    "  --top K                 print only the K most frequent words\n"
+    "  --top K                 print only the K most frequent words (GPU paths: selected on\n"
+    "                          the device, only K rows are copied to the host)\n"
     "  --synthetic SIZE[:SEED[:VOCAB[:ZIPF[:LONGFRAC]]]]  count generated text instead of FILE\n"
     "  --chunk-bytes N         device chunk size (default 1G)\n"
     "  --host-staged           stream FILE through the pinned host ring (no echo)\n"
@@ -165,6 +166,9 @@ int run(const Cli& c) {
   uint64_t bytes = 0;
   int gpus_used = 0, ranks_used = 0;
   wc::Stats stages;  // GPU path: stage timings (max over ranks) and counters (sums)
+  // keys of the whole table: with --top / --no-list the GPU paths fetch only the rows they print
+  uint64_t table_keys = 0;
+  bool keys_known = false;
 
   const bool need_host_text = !c.synthetic && (c.echo || c.cpu || c.compat);
   if (!c.synthetic) {
@@ -265,9 +269,27 @@ int run(const Cli& c) {
           wc::FileSource src(c.file, sr.begin, sr.end);
           eng.count_source(src, sr.begin);
         }
-        wc::KeyTable kt = eng.result(g > 1 ? comms[r].get() : nullptr, false);
+        // Rows: everything unless the listing needs fewer — --no-list none, --top K
+        // the K most frequent, selected on the device (decided once the finalize
+        // has the key count: K >= keys lists in first-occurrence order, as --top 0)
+        wc::Comm* cm = g > 1 ? comms[r].get() : nullptr;
+        wc::KeyTable kt;
+        uint64_t keys = 0;
+        if (!c.list) {
+          kt = eng.top_k(0, cm, false, &keys);
+        } else if (c.top > 0) {
+          keys = eng.finalize_device(cm);
+          if (r == 0) kt = eng.finalized_rows(c.top);
+        } else {
+          kt = eng.result(cm, false);
+          keys = kt.size();
+        }
         rank_stats[r] = eng.stats();
-        if (r == 0) t = std::move(kt);
+        if (r == 0) {
+          t = std::move(kt);
+          table_keys = keys;
+          keys_known = true;
+        }
       } catch (const std::exception& ex) {
         errs[r] = ex.what();
         // peers may be blocked in (or heading into) the merge collectives:
@@ -303,6 +325,7 @@ int run(const Cli& c) {
       stages.table_splits += x.table_splits;
     }
   }
+  if (!keys_known) table_keys = t.size();
   const double secs = wc::now_seconds() - t0;
   write_out(wc::format_output(t, have_text ? reinterpret_cast<const uint8_t*>(text.data()) : nullptr,
                               have_text ? text.size() : 0, c.echo && have_text, c.list, c.top));
@@ -315,7 +338,7 @@ int run(const Cli& c) {
                 "\"device_ms\": {\"map\": %.3f, \"reduce\": %.3f, \"finalize\": %.3f, \"merge\": %.3f, "
                 "\"total\": %.3f}, "
                 "\"chunks\": %u, \"records\": %llu, \"map_reruns\": %u, \"table_splits\": %u}",
-                (unsigned long long)bytes, (unsigned long long)t.total, t.size(), secs, bytes / secs / 1e9,
+                (unsigned long long)bytes, (unsigned long long)t.total, (size_t)table_keys, secs, bytes / secs / 1e9,
                 t.total / secs, gpu_path ? gpus_used : 0, gpu_path ? ranks_used : 0,
                 c.virtual_ranks > 0 ? "true" : "false", c.compat ? "compat" : (c.cpu ? "cpu" : "gpu"),
                 stages.host_count_ms / 1e3, stages.host_count_ms > 0 ? bytes / (stages.host_count_ms * 1e6) : 0.0,
