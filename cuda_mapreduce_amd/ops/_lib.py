@@ -58,6 +58,8 @@ def _load() -> ctypes.CDLL:
         "wc_debug_order": (c_int, [c_int, c_int, P64, c_uint64, c_int, P64, POINTER(ctypes.c_uint32),
                                    POINTER(c_int), POINTER(ctypes.c_double), P64]),
         "wc_debug_top_k": (c_int, [c_int, P64, c_uint64, c_uint64, POINTER(ctypes.c_uint32), P64, P64]),
+        "wc_debug_word_order": (c_int, [c_int, P8, P64, c_uint64, POINTER(ctypes.c_uint32), POINTER(ctypes.c_uint32),
+                                        P64, P64, POINTER(c_double), POINTER(c_double)]),
         "wc_default_options": (None, [POINTER(Options)]),
         "wc_engine_create": (c_void_p, [POINTER(Options)]),
         "wc_engine_destroy": (None, [c_void_p]),
@@ -76,12 +78,14 @@ def _load() -> ctypes.CDLL:
         "wc_finalize_device": (c_int, [c_void_p, c_void_p, P64]),
         "wc_engine_result": (c_void_p, [c_void_p, c_void_p, c_int]),
         "wc_engine_top_k": (c_void_p, [c_void_p, c_void_p, c_int, c_uint64]),
+        "wc_engine_result_by_word": (c_void_p, [c_void_p, c_void_p, c_int]),
         "wc_engine_stats_json": (c_int, [c_void_p, c_char_p, c_int]),
         "wc_engine_sync": (c_int, [c_void_p]),
         "wc_result_size": (c_uint64, [c_void_p]),
         "wc_result_total": (c_uint64, [c_void_p]),
         "wc_result_bytes": (c_uint64, [c_void_p]),
         "wc_result_export": (None, [c_void_p, P64, P64, P64, POINTER(c_char)]),
+        "wc_result_sort_by_word": (c_int, [c_void_p]),
         "wc_result_free": (None, [c_void_p]),
         "wc_format": (c_int, [c_void_p, P8, c_uint64, c_int, c_int, c_uint64, POINTER(c_void_p), P64]),
         "wc_free": (None, [c_void_p]),

@@ -51,6 +51,15 @@ class Result:
         return Result([self.words[i] for i in order], np.asarray(self.counts, np.uint64)[idx],
                       np.asarray(self.first_off, np.uint64)[idx], self.total)
 
+    def by_word(self) -> "Result":
+        """Every row in plain bytewise order of the words (``sorted`` on ``bytes``:
+        bytes compare unsigned, a proper prefix comes first); ``total`` stays.
+        Pure Python on the host: the oracle of ``Engine.result(order="word")``."""
+        order = sorted(range(len(self)), key=self.words.__getitem__)
+        idx = np.asarray(order, dtype=np.int64)
+        return Result([self.words[i] for i in order], np.asarray(self.counts, np.uint64)[idx],
+                      np.asarray(self.first_off, np.uint64)[idx], self.total)
+
     @classmethod
     def _from_native(cls, p) -> "Result":
         try:
@@ -235,8 +244,18 @@ class Engine:
         check(lib.wc_job_resident(self._p, nbytes, global_base, comm._p if comm else None, ctypes.byref(n)))
         return int(n.value)
 
-    def result(self, comm: Optional[Comm] = None, all_ranks: bool = False) -> Result:
-        return Result._from_native(check_ptr(lib.wc_engine_result(self._p, comm._p if comm else None, int(all_ranks))))
+    def result(self, comm: Optional[Comm] = None, all_ranks: bool = False, order: str = "first") -> Result:
+        """Merge, finalize and download the table.  ``order="first"``: rows by first
+        occurrence; ``order="word"``: rows in plain bytewise order of the words
+        (``Result.by_word``), ordered on the GPU.  The device table stays intact:
+        ``result``, ``top_k`` and another order may follow."""
+        if order == "first":
+            fn = lib.wc_engine_result
+        elif order == "word":
+            fn = lib.wc_engine_result_by_word
+        else:
+            raise ValueError(f"order must be 'first' or 'word', got {order!r}")
+        return Result._from_native(check_ptr(fn(self._p, comm._p if comm else None, int(all_ranks))))
 
     def top_k(self, k: int, comm: Optional[Comm] = None, all_ranks: bool = False) -> Result:
         """Finalize as ``result`` does, then select the ``min(k, keys)`` most frequent
@@ -358,6 +377,32 @@ def debug_top_k(counts: np.ndarray, k: int, device: int = 0):
                              rows.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), ctypes.byref(n_out),
                              ctypes.byref(total)))
     return rows[:int(n_out.value)], int(total.value)
+
+
+def debug_word_order(words: Sequence[bytes], device: int = 0, details: bool = False):
+    """Kernel test hook (src/kernels/wordorder.hip) on a list of distinct, non-empty
+    words -> (perm, levels): ``perm[i]`` = the index of the word i-th in plain
+    bytewise order, ``levels`` = the level iterations the device order took.
+    ``details``: a third value, a dict with the words still tied after level 0
+    and the rows, host ms and device ms of each of the first 16 levels."""
+    n = len(words)
+    offs = np.zeros(n + 1, np.uint64)
+    offs[1:] = np.cumsum(np.fromiter(map(len, words), np.int64, n))
+    blob = np.frombuffer(b"".join(words) or b"\0", dtype=np.uint8)
+    perm = np.zeros(max(n, 1), np.uint32)
+    levels, unresolved = ctypes.c_uint32(0), ctypes.c_uint64(0)
+    rows, ms, dev_ms = np.zeros(16, np.uint64), np.zeros(16, np.float64), np.zeros(16, np.float64)
+    PD = ctypes.POINTER(ctypes.c_double)
+    check(lib.wc_debug_word_order(device, blob.ctypes.data_as(_P8), offs.ctypes.data_as(_P64), n,
+                                  perm.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), ctypes.byref(levels),
+                                  ctypes.byref(unresolved), rows.ctypes.data_as(_P64) if details else None,
+                                  ms.ctypes.data_as(PD) if details else None,
+                                  dev_ms.ctypes.data_as(PD) if details else None))
+    if not details:
+        return perm[:n], int(levels.value)
+    k = min(int(levels.value), 16)
+    return perm[:n], int(levels.value), {"unresolved": int(unresolved.value), "rows": rows[:k].tolist(),
+                                         "host_ms": ms[:k].tolist(), "device_ms": dev_ms[:k].tolist()}
 
 
 def shard_range(data: bytes, rank: int, world: int):

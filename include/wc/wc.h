@@ -49,6 +49,14 @@ int wc_debug_order(int device, int method, const uint64_t* keys, uint64_t n, int
  * descending, row ascending), in that order; *sum = the column's sum. */
 int wc_debug_top_k(int device, const uint64_t* counts, uint64_t n, uint64_t k, uint32_t* rows, uint64_t* n_out,
                    uint64_t* sum);
+/* Kernel test hook: the device word order (wordorder.hip) alone on n distinct,
+ * non-empty words, word i = bytes [off[i], off[i + 1]): perm[0, n) = the word
+ * indices in plain bytewise order; *levels = level iterations, *unresolved =
+ * words still tied after level 0.  level_rows / level_ms / level_dev_ms
+ * (nullable, 16 entries each): rows sorted, host and device time per level. */
+int wc_debug_word_order(int device, const uint8_t* bytes, const uint64_t* off, uint64_t n, uint32_t* perm,
+                        uint32_t* levels, uint64_t* unresolved, uint64_t* level_rows, double* level_ms,
+                        double* level_dev_ms);
 void wc_default_options(wc_options* o);
 
 wc_engine* wc_engine_create(const wc_options* o);
@@ -91,6 +99,9 @@ wc_result* wc_engine_result(wc_engine* e, wc_comm* comm, int all_ranks);
  * device, in (count descending, first occurrence ascending) order; the result's
  * total (wc_result_total) is the whole table's. */
 wc_result* wc_engine_top_k(wc_engine* e, wc_comm* comm, int all_ranks, uint64_t k);
+/* The same finalize, then every row in plain bytewise order of the words
+ * (bytes unsigned, a proper prefix first), ordered on the device. */
+wc_result* wc_engine_result_by_word(wc_engine* e, wc_comm* comm, int all_ranks);
 /* JSON object with the engine's Stats. Returns required length. */
 int wc_engine_stats_json(wc_engine* e, char* buf, int cap);
 int wc_engine_sync(wc_engine* e);
@@ -100,6 +111,9 @@ uint64_t wc_result_size(const wc_result* r);
 uint64_t wc_result_total(const wc_result* r);
 uint64_t wc_result_bytes(const wc_result* r);
 void wc_result_export(const wc_result* r, uint64_t* counts, uint64_t* first_off, uint64_t* word_off, char* bytes);
+/* Rows into plain bytewise order of the words, on the host (what the CLI's
+ * host paths do for --sort word). */
+int wc_result_sort_by_word(wc_result* r);
 void wc_result_free(wc_result* r);
 /* reference output framing; *out must be released with wc_free */
 int wc_format(const wc_result* r, const uint8_t* echo, uint64_t echo_len, int echo_input, int list_rows,

@@ -54,6 +54,12 @@ struct Stats {
   // the host wall clock of the last top_k()'s selection (after its finalize).
   uint64_t download_bytes = 0;
   double host_topk_ms = 0;
+  // The last result_by_word(): host wall clock of the order, gather and
+  // download (after its finalize), the level iterations of the device order
+  // (level 0 included) and the rows still tied after level 0.
+  double host_word_order_ms = 0;
+  uint32_t word_order_levels = 0;
+  uint64_t word_order_unresolved = 0;
   // Host wall clock of the last job's API calls (count_*, finalize / result).
   double host_count_ms = 0, host_finalize_ms = 0;
   // Device time of the last job's stages, from events on the engine stream
@@ -160,10 +166,15 @@ class Engine {
   // is the whole table's; *n_keys (optional) its key count.  k = 0: no rows.
   // result() or another top_k() may follow: the device table stays intact.
   KeyTable top_k(uint64_t k, Comm* comm = nullptr, bool all_ranks = false, uint64_t* n_keys = nullptr);
+  // The same finalize, then every row in plain bytewise order of the words
+  // (bytes unsigned, a proper prefix first: sort | uniq -c), ordered on the
+  // device.  result(), top_k() or another result_by_word() may follow.
+  KeyTable result_by_word(Comm* comm = nullptr, bool all_ranks = false);
   // Rows of the table the last finalize_device() left on this device, without
   // finalizing again: the `top` most frequent when 0 < top < keys (as top_k),
-  // else every row in first-occurrence order (as result()).
-  KeyTable finalized_rows(uint64_t top = 0);
+  // else every row in first-occurrence order (as result()) or, with by_word,
+  // in word order (as result_by_word()).
+  KeyTable finalized_rows(uint64_t top = 0, bool by_word = false);
 
   // Device-side finalisation only (no download): returns distinct keys.  Used
   // by the benchmark to time the full pipeline to an ordered device table.
@@ -218,5 +229,8 @@ std::vector<uint8_t> synth_host(uint64_t n, uint64_t first_segment, const SynthS
 // Reference-identical output framing (/root/reference/main.cu:166-218).
 std::string format_output(const KeyTable& t, const uint8_t* echo, uint64_t echo_len, bool echo_input,
                           bool list_rows, uint64_t top_k = 0);
+// Rows into plain bytewise order of the words (the host twin of
+// Engine::result_by_word): bytes compare unsigned, a proper prefix comes first.
+void sort_by_word(KeyTable& t);
 
 }  // namespace wc

@@ -424,6 +424,79 @@ int wc_debug_top_k(int device, const uint64_t* counts, uint64_t n, uint64_t k, u
   });
 }
 
+// Word order (kernels/wordorder.hip) of n given words: the key columns (k0, k1, arena
+// offset and length) and an arena of the LONG words are built with key_of, the
+// device order runs alone.
+int wc_debug_word_order(int device, const uint8_t* bytes, const uint64_t* off, uint64_t n, uint32_t* perm,
+                        uint32_t* levels, uint64_t* unresolved, uint64_t* level_rows, double* level_ms,
+                        double* level_dev_ms) {
+  return guard([&] {
+    WC_HIP_CHECK(hipSetDevice(device));
+    hipStream_t s = nullptr;
+    const size_t nn = n ? n : 1;
+    std::vector<uint64_t> k0(nn), k1(nn), soff(nn);
+    std::vector<uint32_t> slen(nn);
+    std::vector<uint8_t> arena;
+    for (uint64_t i = 0; i < n; ++i) {
+      const uint64_t len = off[i + 1] - off[i];
+      WC_CHECK(len > 0 && len < (1ull << 32), "debug_word_order: words are non-empty and shorter than 4 GiB");
+      wc::key_of(bytes + off[i], len, &k0[i], &k1[i]);
+      soff[i] = 0;
+      slen[i] = 0;
+      if (wc::key_is_hashed(k1[i])) {
+        soff[i] = arena.size();
+        slen[i] = (uint32_t)len;
+        arena.insert(arena.end(), bytes + off[i], bytes + off[i + 1]);
+      }
+    }
+    const size_t ab = arena.size(), ws_bytes = wc::word_order_ws_bytes(n);
+    uint8_t* mem = nullptr;
+    wc::dev_malloc(&mem, 3 * (nn * 8 + 256) + nn * 4 + 256 + ab + 256 + 256 + ws_bytes);
+    uint8_t* p = mem;
+    auto take = [&](size_t b) {
+      uint8_t* r = p;
+      p += (b + 255) / 256 * 256;
+      return r;
+    };
+    uint64_t* dk0 = reinterpret_cast<uint64_t*>(take(nn * 8));
+    uint64_t* dk1 = reinterpret_cast<uint64_t*>(take(nn * 8));
+    uint64_t* dsoff = reinterpret_cast<uint64_t*>(take(nn * 8));
+    uint32_t* dslen = reinterpret_cast<uint32_t*>(take(nn * 4));
+    uint8_t* darena = take(ab ? ab : 1);
+    unsigned long long* err = reinterpret_cast<unsigned long long*>(take(8));
+    void* ws = take(ws_bytes);
+    WC_HIP_CHECK(hipMemcpy(dk0, k0.data(), n * 8, hipMemcpyHostToDevice));
+    WC_HIP_CHECK(hipMemcpy(dk1, k1.data(), n * 8, hipMemcpyHostToDevice));
+    WC_HIP_CHECK(hipMemcpy(dsoff, soff.data(), n * 8, hipMemcpyHostToDevice));
+    WC_HIP_CHECK(hipMemcpy(dslen, slen.data(), n * 4, hipMemcpyHostToDevice));
+    if (ab) WC_HIP_CHECK(hipMemcpy(darena, arena.data(), ab, hipMemcpyHostToDevice));
+    WC_HIP_CHECK(hipMemset(err, 0, 8));
+    wc::WordOrderInfo info;
+    info.time_events = level_dev_ms != nullptr;
+    std::string failed;
+    unsigned long long bw = 0;
+    try {
+      const uint32_t* d = wc::word_order(wc::WordCols{dk0, dk1, dsoff, dslen, n, darena, ab}, ws, s, err, nullptr,
+                                         &info);
+      bw = info.bounds_word;
+      if (!bw && n) WC_HIP_CHECK(hipMemcpy(perm, d, n * 4, hipMemcpyDeviceToHost));
+    } catch (const std::exception& ex) {
+      failed = ex.what();
+    }
+    WC_HIP_CHECK(hipFree(mem));
+    if (!failed.empty()) wc::fail(failed);
+    WC_CHECK(bw == 0, std::string("bounds guard: ") + wc::bounds_kernel_name((uint32_t)(bw >> 56)) + " reached row " +
+                          std::to_string(bw & ((1ull << 56) - 1)) + " past its buffer");
+    *levels = info.levels;
+    *unresolved = info.unresolved;
+    for (uint32_t l = 0; l < wc::WordOrderInfo::MAX_LEVEL_ROWS; ++l) {
+      if (level_rows) level_rows[l] = info.level_rows[l];
+      if (level_ms) level_ms[l] = info.level_ms[l];
+      if (level_dev_ms) level_dev_ms[l] = info.level_dev_ms[l];
+    }
+  });
+}
+
 int wc_device_count(void) {
   int n = 0;
   if (hipGetDeviceCount(&n) != hipSuccess) return 0;
@@ -555,6 +628,15 @@ wc_result* wc_engine_top_k(wc_engine* e, wc_comm* c, int all_ranks, uint64_t k) 
   return r;
 }
 
+wc_result* wc_engine_result_by_word(wc_engine* e, wc_comm* c, int all_ranks) {
+  wc_result* r = new wc_result;
+  if (guard([&] { r->t = e->e->result_by_word(c ? c->c.get() : nullptr, all_ranks != 0); }) != 0) {
+    delete r;
+    return nullptr;
+  }
+  return r;
+}
+
 int wc_engine_stats_json(wc_engine* e, char* buf, int cap) {
   const wc::Stats& s = e->e->stats();
   char tmp[2048];
@@ -565,14 +647,16 @@ int wc_engine_stats_json(wc_engine* e, char* buf, int cap) {
                          "\"merges_planned\": %u, \"merge_redos\": %u, \"download_bytes\": %llu, "
                          "\"device_ms\": {\"map\": %.4f, \"reduce\": %.4f, \"finalize\": %.4f, \"merge\": %.4f, "
                          "\"idle\": %.4f, \"total\": %.4f}, "
-                         "\"host_ms\": {\"count\": %.4f, \"finalize\": %.4f, \"top_k\": %.4f}}",
+                         "\"host_ms\": {\"count\": %.4f, \"finalize\": %.4f, \"top_k\": %.4f, "
+                         "\"word_order\": %.4f}, \"word_order\": {\"levels\": %u, \"unresolved\": %llu}}",
                          (unsigned long long)s.bytes, (unsigned long long)s.tokens, (unsigned long long)s.keys,
                          (unsigned long long)s.records, (unsigned long long)s.long_tokens, s.long_direct, s.chunks,
                          s.map_reruns, s.table_splits, s.log2_buckets, s.order_path,
                          s.merges_planned, s.merge_redos, (unsigned long long)s.download_bytes,
                          s.map_ms,
                          s.reduce_ms, s.finalize_ms, s.merge_ms, s.idle_ms, s.device_ms, s.host_count_ms,
-                         s.host_finalize_ms, s.host_topk_ms);
+                         s.host_finalize_ms, s.host_topk_ms, s.host_word_order_ms, s.word_order_levels,
+                         (unsigned long long)s.word_order_unresolved);
   if (buf && cap > 0) {
     std::strncpy(buf, tmp, (size_t)cap - 1);
     buf[cap - 1] = 0;
@@ -606,6 +690,8 @@ void wc_result_export(const wc_result* r, uint64_t* counts, uint64_t* first_off,
   }
   if (word_off) word_off[r->t.size()] = o;
 }
+
+int wc_result_sort_by_word(wc_result* r) { return guard([&] { wc::sort_by_word(r->t); }); }
 
 void wc_result_free(wc_result* r) { delete r; }
 

@@ -1095,19 +1095,19 @@ void Engine::Impl::sort_cols_by_first(bool radix) {
   st.order_path = radix ? 3 : 2;
 }
 
-KeyTable Engine::Impl::download_cols() {
+KeyTable Engine::Impl::download_cols(const KeyCols& c) {
   Range r("wc_download");
-  const uint64_t n = cols.n;
+  const uint64_t n = c.n;
   std::vector<uint64_t> k0(n), k1(n), cnt(n), first(n), soff(n);
   std::vector<uint32_t> slen(n);
   std::vector<uint8_t> arena(cols_arena_bytes);
   if (n) {
-    WC_HIP_CHECK(hipMemcpyAsync(k0.data(), cols.k0, n * 8, hipMemcpyDeviceToHost, s));
-    WC_HIP_CHECK(hipMemcpyAsync(k1.data(), cols.k1, n * 8, hipMemcpyDeviceToHost, s));
-    WC_HIP_CHECK(hipMemcpyAsync(cnt.data(), cols.cnt, n * 8, hipMemcpyDeviceToHost, s));
-    WC_HIP_CHECK(hipMemcpyAsync(first.data(), cols.first, n * 8, hipMemcpyDeviceToHost, s));
-    WC_HIP_CHECK(hipMemcpyAsync(soff.data(), cols.sref_off, n * 8, hipMemcpyDeviceToHost, s));
-    WC_HIP_CHECK(hipMemcpyAsync(slen.data(), cols.sref_len, n * 4, hipMemcpyDeviceToHost, s));
+    WC_HIP_CHECK(hipMemcpyAsync(k0.data(), c.k0, n * 8, hipMemcpyDeviceToHost, s));
+    WC_HIP_CHECK(hipMemcpyAsync(k1.data(), c.k1, n * 8, hipMemcpyDeviceToHost, s));
+    WC_HIP_CHECK(hipMemcpyAsync(cnt.data(), c.cnt, n * 8, hipMemcpyDeviceToHost, s));
+    WC_HIP_CHECK(hipMemcpyAsync(first.data(), c.first, n * 8, hipMemcpyDeviceToHost, s));
+    WC_HIP_CHECK(hipMemcpyAsync(soff.data(), c.sref_off, n * 8, hipMemcpyDeviceToHost, s));
+    WC_HIP_CHECK(hipMemcpyAsync(slen.data(), c.sref_len, n * 4, hipMemcpyDeviceToHost, s));
   }
   if (!arena.empty())
     WC_HIP_CHECK(hipMemcpyAsync(arena.data(), cols_arena, arena.size(), hipMemcpyDeviceToHost, s));
@@ -1229,6 +1229,64 @@ KeyTable Engine::Impl::select_top(uint64_t k) {
   st.host_topk_ms = (now_seconds() - t0) * 1e3;
   WC_LOG(LOG_INFO, "dev %d: top_k %.3f ms (host), k %llu of %llu keys, %llu bytes to the host", dev, st.host_topk_ms,
          (unsigned long long)k, (unsigned long long)n, (unsigned long long)st.download_bytes);
+  return t;
+}
+
+// Every row of the finalized columns in plain bytewise order of the words:
+// the permutation on the device (kernels/wordorder.hip: one host wait per
+// level), the six columns gathered through it into word_mem, and those
+// downloaded.  cols and the key arena are only read.
+KeyTable Engine::Impl::order_by_word() {
+  Range r("wc_word_order");
+  const double t0 = now_seconds();
+  WC_HIP_CHECK(hipSetDevice(dev));
+  WC_CHECK(cols.dn == nullptr && cols.occ == nullptr, "result_by_word needs finalized columns");
+  const uint64_t n = cols.n, nn = n ? n : 1;
+  struct Stage {
+    Impl* im;
+    uint64_t n;
+  } sa{this, n};
+  auto stage = [](void* a, const char* what) {  // WC_SYNC_DEBUG: attribute a device fault to a stage
+    Stage& x = *static_cast<Stage*>(a);
+    const hipError_t e = hipStreamSynchronize(x.im->s);
+    fprintf(stderr, "[wc] word_order  %s n=%llu -> %s\n", what, (unsigned long long)x.n, hipGetErrorString(e));
+  };
+  DeviceArena& A = word_mem;
+  const size_t ws_bytes = word_order_ws_bytes(n);
+  A.reset();
+  A.reserve(ws_bytes + nn * (5 * 8 + 4) + 16 * 256);
+  void* ws = A.take(ws_bytes);
+  KeyCols o;
+  o.k0 = A.take_n<uint64_t>(nn);
+  o.k1 = A.take_n<uint64_t>(nn);
+  o.cnt = A.take_n<uint64_t>(nn);
+  o.first = A.take_n<uint64_t>(nn);
+  o.sref_off = A.take_n<uint64_t>(nn);
+  o.sref_len = A.take_n<uint32_t>(nn);
+  o.n = n;
+  h_word.resize(128);
+  WordOrderInfo info;
+  const WordCols wc{cols.k0, cols.k1, cols.sref_off, cols.sref_len, n, cols_arena, cols_arena_bytes};
+  const uint32_t* perm = word_order(wc, ws, s, d_bounds, reinterpret_cast<unsigned long long*>(h_word.data()), &info,
+                                    sync_debug ? +stage : nullptr, &sa);
+  check_bounds(info.bounds_word, "the word order");
+  launch_gather_cols(cols.k0, cols.k1, cols.cnt, cols.first, cols.sref_off, cols.sref_len, perm, o.k0, o.k1, o.cnt,
+                     o.first, o.sref_off, o.sref_len, n, s, nullptr, bounds(n));
+  if (sync_debug) stage(&sa, "gather");
+  WC_HIP_CHECK(hipMemcpyAsync(h_word.data() + 64, d_bounds, 8, hipMemcpyDeviceToHost, s));
+  KeyTable t = download_cols(o);  // waits for the stream
+  uint64_t bw = 0;
+  std::memcpy(&bw, h_word.data() + 64, 8);
+  check_bounds(bw, "the word order's gather");
+  st.word_order_levels = info.levels;
+  st.word_order_unresolved = info.unresolved;
+  st.host_word_order_ms = (now_seconds() - t0) * 1e3;
+  if (log_level() >= LOG_INFO)
+    for (uint32_t l = 0; l < std::min<uint32_t>(info.levels, WordOrderInfo::MAX_LEVEL_ROWS); ++l)
+      WC_LOG(LOG_INFO, "dev %d: word order level %u: %llu rows, %.3f ms (host)", dev, l,
+             (unsigned long long)info.level_rows[l], info.level_ms[l]);
+  WC_LOG(LOG_INFO, "dev %d: word order %.3f ms (host), %llu keys, %u level(s), %llu tied after level 0", dev,
+         st.host_word_order_ms, (unsigned long long)n, info.levels, (unsigned long long)info.unresolved);
   return t;
 }
 
@@ -1704,7 +1762,17 @@ KeyTable Engine::result(Comm* comm, bool all_ranks) {
     KeyTable t;
     return t;
   }
-  return im.download_cols();
+  return im.download_cols(im.cols);
+}
+
+KeyTable Engine::result_by_word(Comm* comm, bool all_ranks) {
+  Impl& im = *p_;
+  im.finalize(comm, all_ranks);
+  if (comm && comm->size() > 1 && comm->rank() != 0 && !all_ranks) {
+    KeyTable t;
+    return t;
+  }
+  return im.order_by_word();
 }
 
 KeyTable Engine::top_k(uint64_t k, Comm* comm, bool all_ranks, uint64_t* n_keys) {
@@ -1719,10 +1787,12 @@ KeyTable Engine::top_k(uint64_t k, Comm* comm, bool all_ranks, uint64_t* n_keys)
   return im.select_top(k);
 }
 
-KeyTable Engine::finalized_rows(uint64_t top) {
+KeyTable Engine::finalized_rows(uint64_t top, bool by_word) {
   Impl& im = *p_;
   WC_HIP_CHECK(hipSetDevice(im.dev));
-  return top && top < im.cols.n ? im.select_top(top) : im.download_cols();
+  WC_CHECK(!(by_word && top), "finalized_rows: the most frequent rows come by count, not by word");
+  if (by_word) return im.order_by_word();
+  return top && top < im.cols.n ? im.select_top(top) : im.download_cols(im.cols);
 }
 
 }  // namespace wc

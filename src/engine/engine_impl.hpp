@@ -322,7 +322,7 @@ struct Engine::Impl {
   uint32_t* fo_ovf = nullptr;  // overflow word of the sample sort sort_cols_by_first left in flight
   KeyCols cols_unsorted;       // its input, kept for a radix redo
   bool order_redo = false;     // the speculative finalize's sample sort overflowed (Stats::order_path 4)
-  KeyTable download_cols();
+  KeyTable download_cols(const KeyCols& c);  // c's rows (their words in cols_arena) to the host
   // Top-K selection on the finalized columns (kernels/topk.hip): its own
   // workspace, grown on demand and kept across calls — cols and the arena are
   // only read, so result() and another top_k() may follow.
@@ -331,6 +331,14 @@ struct Engine::Impl {
   PinnedBuffer h_topk_st;  // TopkState + the bounds word
   PinnedBuffer h_topk;     // the K rows and their words
   KeyTable select_top(uint64_t k);
+  // Word order of the finalized columns (kernels/wordorder.hip): the
+  // permutation's workspace and the ordered copy of the six columns live in
+  // their own arena — cols stays in first-occurrence order and the key arena
+  // is neither copied nor reordered (sref_off stays valid), so result(),
+  // top_k() and another result_by_word() may follow.
+  DeviceArena word_mem;
+  PinnedBuffer h_word;  // WordState + the bounds word, read after every level
+  KeyTable order_by_word();
 };
 
 // Multi-rank merge (dist/merge.cpp): replaces im.cols / cols_arena with the

@@ -7,6 +7,7 @@
 //   wc_table_compact  running table -> dense key list
 //   wc_radix_*        LSD radix sort (first-occurrence order, merge dictionary)
 //   wc_topk_*         the K most frequent rows of the ordered table (Engine::top_k)
+//   wc_word_*         the ordered table's rows by word, bytewise (Engine::result_by_word)
 //   wc_synth_text     device-side synthetic text generator
 // Reference counterparts: mapKernel (/root/reference/main.cu:109-117) and the
 // single-thread reduceKernel (main.cu:119-123).
@@ -286,6 +287,12 @@ enum BoundsKernel : uint32_t {
   BND_TOPK_RANK,     // topk.hip wc_topk_rank: ordered row indices
   BND_TOPK_GATHER,   // topk.hip wc_topk_gather: output rows and table rows
   BND_TOPK_WORDS,    // topk.hip wc_topk_words: blob bytes and arena bytes
+  BND_WORD_KEYS,     // wordorder.hip wc_word_init / wc_word_chunk / wc_word_keys: slots and table rows
+  BND_WORD_MARK,     // wordorder.hip wc_word_mark / wc_word_write: sorted slot indices
+  BND_WORD_PERM,     // wordorder.hip wc_word_mark: output positions
+  BND_WORD_COMPACT,  // wordorder.hip wc_word_write: the next level's slots and segments
+  BND_WORD_LCP,      // wordorder.hip wc_word_lcp: segment bounds and table rows
+  BND_WORD_ARENA,    // wordorder.hip: arena bytes of a LONG word's chunk
   BND_KERNELS
 };
 struct Bounds {
@@ -439,6 +446,44 @@ void topk_gather(const TopkSrc& src, const uint32_t* rows, uint64_t m, const Top
                  const Bounds& bnd = {});
 void topk_words(const uint8_t* arena, uint64_t arena_bytes, const TopkDst& dst, uint64_t m, uint8_t* blob,
                 uint64_t blob_bytes, unsigned long long* err, hipStream_t s);
+
+// ---- word order (wordorder.hip): the rows of finalized columns by word ----
+// Plain bytewise order of the words (bytes unsigned, a proper prefix first),
+// as a permutation of row indices.  One host wait per level; level 0 orders
+// every row by its first 8 bytes, later levels only the rows still tied.
+struct WordCols {
+  const uint64_t *k0, *k1, *soff;
+  const uint32_t* slen;
+  uint64_t n;            // rows, < 2^32
+  const uint8_t* arena;  // the bytes of the LONG words
+  uint64_t arena_bytes;
+};
+struct WordState {  // 64 bytes, zeroed by word_order; read by the host after every level
+  unsigned long long unresolved;  // rows still tied after the level (the next level's slots)
+  unsigned long long segments;    // the runs they form
+  unsigned long long dup;         // nonzero: rows dup_a and dup_b hold the same word
+  unsigned long long dup_a, dup_b;
+  unsigned long long pad[3];
+};
+struct WordOrderInfo {
+  static constexpr uint32_t MAX_LEVEL_ROWS = 16;
+  uint32_t levels = 0;         // level iterations, level 0 included
+  uint64_t unresolved = 0;     // rows still tied after level 0
+  uint64_t bounds_word = 0;    // nonzero: a writer met a row past its buffer; the permutation is invalid
+  uint64_t level_rows[MAX_LEVEL_ROWS] = {};  // rows each of the first levels sorted
+  double level_ms[MAX_LEVEL_ROWS] = {};      // their host wall time, the level's wait included
+  bool time_events = false;                  // in: also measure them with stream events
+  double level_dev_ms[MAX_LEVEL_ROWS] = {};  // the levels' device time (time_events)
+};
+size_t word_order_ws_bytes(uint64_t n);
+// Returns the permutation (n rows, inside ws): row perm[i] is i-th by word.
+// bounds_err (nullable): the bounds guard's word; h_state (nullable): 9 words
+// of page-locked host memory for the per-level read; stage (nullable): called
+// after each group of launches (WC_SYNC_DEBUG attribution).  A duplicate word
+// in the table fails the job naming the two rows.
+const uint32_t* word_order(const WordCols& c, void* ws, hipStream_t s, unsigned long long* bounds_err = nullptr,
+                           unsigned long long* h_state = nullptr, WordOrderInfo* info = nullptr,
+                           void (*stage)(void*, const char*) = nullptr, void* stage_arg = nullptr);
 
 // util.hip: fill several device regions (+ a few small copies, e.g. host words
 // from page-locked memory into device buffers) / copy several small device

@@ -1506,7 +1506,9 @@ void launch_table_compact(const TableView& t, const uint64_t* bucket_off, uint64
 const char* bounds_kernel_name(uint32_t k) {
   static const char* names[BND_KERNELS] = {"none",           "wc_fo_sort",    "wc_bm_place",      "wc_bm_emit",
                                            "wc_gather_cols", "wc_table_keys", "wc_gather_table", "wc_table_compact",
-                                           "wc_topk_write",  "wc_topk_rank",  "wc_topk_gather",  "wc_topk_words"};
+                                           "wc_topk_write",  "wc_topk_rank",  "wc_topk_gather",  "wc_topk_words",
+                                           "wc_word_keys",   "wc_word_mark",  "wc_word_perm",    "wc_word_write",
+                                           "wc_word_lcp",    "wc_word_chunk (arena)"};
   return k < BND_KERNELS ? names[k] : "unknown";
 }
 

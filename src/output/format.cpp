@@ -10,6 +10,7 @@
 // Counts are u64 (the reference's int overflows at 2^31).  `list_rows=false`
 // and `top_k` exist for multi-GB inputs whose tables have millions of rows.
 #include <algorithm>
+#include <cstring>
 #include <numeric>
 #include <string>
 
@@ -50,6 +51,28 @@ std::string format_output(const KeyTable& t, const uint8_t* echo, uint64_t echo_
   out += "Total Count:";
   out += num;
   return out;
+}
+
+void sort_by_word(KeyTable& t) {
+  const size_t n = t.size();
+  std::vector<size_t> idx(n);
+  std::iota(idx.begin(), idx.end(), 0);
+  std::sort(idx.begin(), idx.end(), [&](size_t a, size_t b) {
+    const std::string &x = t.words[a], &y = t.words[b];
+    const int c = std::memcmp(x.data(), y.data(), std::min(x.size(), y.size()));  // bytes as unsigned char
+    return c != 0 ? c < 0 : x.size() < y.size();
+  });
+  KeyTable o;
+  o.total = t.total;
+  o.words.reserve(n);
+  o.counts.reserve(n);
+  o.first_off.reserve(n);
+  for (size_t i : idx) {
+    o.words.push_back(std::move(t.words[i]));
+    o.counts.push_back(t.counts[i]);
+    o.first_off.push_back(t.first_off[i]);
+  }
+  t = std::move(o);
 }
 
 }  // namespace wc

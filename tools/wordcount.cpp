@@ -37,6 +37,9 @@ const char* kUsage =
     "  --no-list               do not print per-word rows\n"
     "  --top K                 print only the K most frequent words (GPU paths: selected on\n"
     "                          the device, only K rows are copied to the host)\n"
+    "  --sort first|word       row order: first occurrence (default, as the reference) or\n"
+    "                          plain bytewise order of the words (sort | uniq -c; GPU paths:\n"
+    "                          ordered on the device); not together with --top K\n"
     "  --synthetic SIZE[:SEED[:VOCAB[:ZIPF[:LONGFRAC]]]]  count generated text instead of FILE\n"
     "  --chunk-bytes N         device chunk size (default 1G)\n"
     "  --host-staged           stream FILE through the pinned host ring (no echo)\n"
@@ -69,6 +72,7 @@ struct Cli {
   int virtual_ranks = 0;
   bool cpu = false, compat = false, echo = true, list = true, host_staged = false;
   uint64_t top = 0, chunk = 1ull << 30;
+  bool sort_word = false;
   uint32_t merge_mode = 0;
   bool synthetic = false;
   uint64_t synth_bytes = 0;
@@ -105,6 +109,12 @@ Cli parse(int argc, char** argv) {
     else if (a == "--no-echo") c.echo = false;
     else if (a == "--no-list") c.list = false;
     else if (a == "--top") c.top = std::stoull(need("--top"));
+    else if (a == "--sort") {
+      const std::string m = need("--sort");
+      if (m == "first") c.sort_word = false;
+      else if (m == "word") c.sort_word = true;
+      else wc::fail("--sort expects first or word, got " + m);
+    }
     else if (a == "--chunk-bytes") c.chunk = parse_size(need("--chunk-bytes"));
     else if (a == "--host-staged") c.host_staged = true;
     else if (a == "--bench-json") c.bench_json = need("--bench-json");
@@ -130,6 +140,9 @@ Cli parse(int argc, char** argv) {
   if (c.synthetic) c.echo = false;
   if (!c.ckpt.empty() && (c.synthetic || c.compat)) wc::fail("--checkpoint needs a FILE input and the clean semantics");
   if (c.resume && c.ckpt.empty()) wc::fail("--resume needs --checkpoint PATH");
+  if (c.sort_word && c.top > 0)
+    wc::fail("--sort word cannot be combined with --top K: --top lists by count (the K most frequent words in "
+             "word order is not implemented)");
   if (c.gpus < 1) wc::fail("--gpus expects N >= 1");
   if (c.virtual_ranks < 0 || c.virtual_ranks > 64) wc::fail("--virtual-ranks expects 1..64");
   if (c.virtual_ranks && c.gpus != 1) wc::fail("--virtual-ranks runs on one GPU: drop --gpus");
@@ -280,6 +293,9 @@ int run(const Cli& c) {
         } else if (c.top > 0) {
           keys = eng.finalize_device(cm);
           if (r == 0) kt = eng.finalized_rows(c.top);
+        } else if (c.sort_word) {  // ordered on the device
+          kt = eng.result_by_word(cm, false);
+          keys = kt.size();
         } else {
           kt = eng.result(cm, false);
           keys = kt.size();
@@ -326,6 +342,8 @@ int run(const Cli& c) {
     }
   }
   if (!keys_known) table_keys = t.size();
+  // host paths (CPU oracle, reference emulation, checkpointed runs merged on the host): the same order on the host
+  if (c.sort_word && c.list && (c.cpu || c.compat || !c.ckpt.empty())) wc::sort_by_word(t);
   const double secs = wc::now_seconds() - t0;
   write_out(wc::format_output(t, have_text ? reinterpret_cast<const uint8_t*>(text.data()) : nullptr,
                               have_text ? text.size() : 0, c.echo && have_text, c.list, c.top));
