@@ -34,6 +34,8 @@ class Options(ctypes.Structure):
         ("records_per_byte", c_double),
         ("merge_mode", c_uint32),  # 0 shuffle (all-to-all by key owner), 1 dense reduce-scatter
         ("k1_hash_bits", c_uint32),  # tests: LONG-word hash bits kept (0 = all) to force collisions
+        ("byte_map", ctypes.c_uint8 * 256),  # translation table applied on the GPU before tokenizing ...
+        ("byte_map_on", c_uint32),  # ... when this is set (default_options(byte_map=...) sets both)
     ]
 
 
@@ -61,6 +63,10 @@ def _load() -> ctypes.CDLL:
         "wc_debug_word_order": (c_int, [c_int, P8, P64, c_uint64, POINTER(ctypes.c_uint32), POINTER(ctypes.c_uint32),
                                         P64, P64, POINTER(c_double), POINTER(c_double)]),
         "wc_default_options": (None, [POINTER(Options)]),
+        "wc_byte_map_check": (c_int, [P8]),
+        "wc_byte_map_build": (c_int, [c_int, P8, c_uint64, c_int, P8]),
+        "wc_debug_translate": (c_int, [c_int, P8, c_uint64, P8, P8, c_uint64]),
+        "wc_cpu_count_mapped": (c_void_p, [P8, c_uint64, c_uint64, P8]),
         "wc_engine_create": (c_void_p, [POINTER(Options)]),
         "wc_engine_destroy": (None, [c_void_p]),
         "wc_engine_reset": (c_int, [c_void_p]),

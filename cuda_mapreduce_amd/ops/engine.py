@@ -96,9 +96,66 @@ def format_output(res: Result, echo: Optional[bytes] = None, list_rows: bool = T
     return bytes(out)
 
 
+def _map_array(m) -> "ctypes.Array":
+    """A 256-entry byte map as a ctypes array; anything but 256 bytes is a ValueError."""
+    if not isinstance(m, (bytes, bytearray, memoryview)) or len(m) != 256:
+        raise ValueError("byte_map must be a bytes object of length 256 (see ops.byte_map), got " +
+                         (f"{len(m)} bytes" if isinstance(m, (bytes, bytearray, memoryview)) else type(m).__name__))
+    return (ctypes.c_uint8 * 256).from_buffer_copy(bytes(m))
+
+
+_PUNCT = tuple(range(0x21, 0x30)) + tuple(range(0x3A, 0x41)) + tuple(range(0x5B, 0x61)) + tuple(range(0x7B, 0x7F))
+
+
+def byte_map(fold_case: bool = False, split: bytes = b"", split_punct: bool = False) -> bytes:
+    """A byte map for ``Engine(byte_map=...)`` / ``cpu_count(byte_map=...)``: 256
+    bytes, as ``bytes.translate`` takes them.  ``fold_case``: ``A``-``Z`` to
+    ``a``-``z`` (ASCII only, bytes >= 0x80 untouched); ``split``: every listed
+    byte to space; ``split_punct``: every ASCII punctuation byte to space.  Every
+    map built here is valid (``check_byte_map``).  The Python twin of the
+    native builder (wc.hpp make_byte_map)."""
+    m = bytearray(range(256))
+    if fold_case:
+        for b in range(ord("A"), ord("Z") + 1):
+            m[b] = b + 32
+    if split_punct:
+        for b in _PUNCT:
+            m[b] = 0x20
+    for b in bytes(split):
+        if b not in (0x20, 0x0D, 0x0A):
+            m[b] = 0x20
+    return bytes(m[m[b]] for b in range(256))  # 'A' -> 'a' -> space when 'a' is split
+
+
+def check_byte_map(m: bytes) -> None:
+    """Raise unless ``m`` is a valid byte map: 256 bytes (ValueError), the three
+    delimiters mapped to themselves and ``m[m[b]] == m[b]`` for every byte
+    (WcError naming the offending byte)."""
+    check(lib.wc_byte_map_check(ctypes.cast(_map_array(m), _P8)))
+
+
+def debug_translate(data: bytes, m: bytes, device: int = 0) -> bytes:
+    """Kernel test hook (src/kernels/translate.hip): ``data`` through the map on
+    the GPU -> the n translated bytes followed by the 64 guard bytes that lay
+    behind them in the device buffer (pre-filled with ``TRANSLATE_GUARD``)."""
+    n = len(data)
+    src = np.frombuffer(bytes(data) or b"\0", dtype=np.uint8)
+    out = np.zeros(n + 64, np.uint8)
+    check(lib.wc_debug_translate(device, src.ctypes.data_as(_P8), n, ctypes.cast(_map_array(m), _P8),
+                                 out.ctypes.data_as(_P8), len(out)))
+    return out.tobytes()
+
+
+TRANSLATE_GUARD = bytes(ord("A") + i % 26 for i in range(64))
+
+
 def default_options(**kw) -> Options:
     o = Options()
     lib.wc_default_options(ctypes.byref(o))
+    m = kw.pop("byte_map", None)
+    if m is not None:  # not a plain field: the table and its switch
+        o.byte_map = _map_array(m)
+        o.byte_map_on = 1
     for k, v in kw.items():
         if not hasattr(o, k):
             raise TypeError(f"unknown engine option {k!r}")
@@ -154,7 +211,11 @@ class Comm:
 
 
 class Engine:
-    """One GPU's MapReduce engine: count text, then merge / order / download."""
+    """One GPU's MapReduce engine: count text, then merge / order / download.
+
+    ``byte_map`` (256 bytes, see ``byte_map()``): the text is translated through it
+    on the GPU before it is tokenized — ``Result.words`` are the translated
+    bytes, ``first_off`` stay offsets in the original text."""
 
     def __init__(self, device: int = 0, **opts):
         self.options = default_options(device=device, **opts)
@@ -290,9 +351,13 @@ def cpu_count_file_checkpointed(path: str, checkpoint: str = "", interval: int =
     return _count_file_checkpointed(None, path, checkpoint, interval, resume, begin, end, 0, 1)
 
 
-def cpu_count(data: bytes, global_base: int = 0) -> Result:
-    """Single-thread CPU oracle (BASELINE config 1)."""
+def cpu_count(data: bytes, global_base: int = 0, byte_map: Optional[bytes] = None) -> Result:
+    """Single-thread CPU oracle (BASELINE config 1).  ``byte_map``: count the text
+    translated through it (the host twin of ``Engine(byte_map=...)``)."""
     ptr, keep = _u8ptr(data)
+    if byte_map is not None:
+        return Result._from_native(check_ptr(lib.wc_cpu_count_mapped(ptr, len(keep), global_base,
+                                                                    ctypes.cast(_map_array(byte_map), _P8))))
     return Result._from_native(check_ptr(lib.wc_cpu_count(ptr, len(keep), global_base)))
 
 

@@ -321,6 +321,7 @@ class DistributedWordCount:
         self.env = env
         self.use_gpu = use_gpu
         self.dense = engine_opts.get("merge_mode", 0) == 1  # CPU ranks: the same protocol choice
+        self.byte_map = engine_opts.get("byte_map")  # the engine translates on the GPU, a CPU rank on the host
         self.engine = Engine(device=env.local_rank, **engine_opts) if use_gpu else None
         self.comm = rccl_comm(env, env.local_rank) if use_gpu else None
 
@@ -332,13 +333,17 @@ class DistributedWordCount:
 
     def count_bytes(self, data: bytes) -> Result:
         b, e = shard_range(data, self.env.rank, self.env.world)
-        return self._count(lambda eng: eng.count_bytes(data[b:e], global_base=b), lambda: cpu_count(data[b:e], b))
+        return self._count(lambda eng: eng.count_bytes(data[b:e], global_base=b),
+                           lambda: cpu_count(data[b:e], b, byte_map=self.byte_map))
 
     def count_file(self, path: str, checkpoint: str = "", interval: int = 4 << 30, resume: bool = True) -> Result:
         """Count a file sharded over the ranks.  With `checkpoint`, every rank counts its
         shard resumably (src/io/checkpoint.cpp; file `<checkpoint>.r<rank>of<world>`) and
         the per-rank host tables are merged with gather_merge."""
         b, e = shard_range_file(path, self.env.rank, self.env.world)
+        if checkpoint and self.byte_map is not None:
+            raise ValueError("checkpointed counting with a byte map is not supported "
+                             "(the checkpoint file does not record the map)")
         if checkpoint:
             if self.use_gpu:
                 local = self.engine.count_file_checkpointed(path, checkpoint, interval, resume, b, e,
@@ -353,7 +358,7 @@ class DistributedWordCount:
         def host():
             with open(path, "rb") as fh:
                 fh.seek(b)
-                return cpu_count(fh.read(e - b), b)
+                return cpu_count(fh.read(e - b), b, byte_map=self.byte_map)
 
         return self._count(lambda eng: eng.count_file(path, b, e), host)
 

@@ -26,6 +26,11 @@ typedef struct wc_options {
   double records_per_byte;
   uint32_t merge_mode; /* 0 shuffle (all-to-all by key owner), 1 dense reduce-scatter */
   uint32_t k1_hash_bits; /* tests: LONG-word hash bits kept (0 = all) to force collisions */
+  /* Byte map (wc.hpp ByteMap): with byte_map_on the text is translated through
+   * byte_map on the GPU before it is tokenized.  wc_engine_create checks it
+   * (wc_byte_map_check). */
+  uint8_t byte_map[256];
+  uint32_t byte_map_on;
 } wc_options;
 
 const char* wc_last_error(void);
@@ -57,7 +62,20 @@ int wc_debug_top_k(int device, const uint64_t* counts, uint64_t n, uint64_t k, u
 int wc_debug_word_order(int device, const uint8_t* bytes, const uint64_t* off, uint64_t n, uint32_t* perm,
                         uint32_t* levels, uint64_t* unresolved, uint64_t* level_rows, double* level_ms,
                         double* level_dev_ms);
-void wc_default_options(wc_options* o);
+void wc_default_options(wc_options* o); /* byte_map: identity, off */
+/* Host only: 0 if m is a valid byte map — the delimiters 0x20, 0x0D, 0x0A map
+ * to themselves and m[m[b]] == m[b] for every b — else -1 and a message naming
+ * the offending byte. */
+int wc_byte_map_check(const uint8_t m[256]);
+/* Host only: the map of the CLI flags / ops.byte_map(): fold_case A-Z -> a-z,
+ * every byte of split[0, split_n) -> space, split_punct every ASCII
+ * punctuation byte -> space.  Valid by construction. */
+int wc_byte_map_build(int fold_case, const uint8_t* split, uint64_t split_n, int split_punct, uint8_t out[256]);
+/* Kernel test hook (translate.hip): `in` copied into a 16-byte-aligned device
+ * buffer of n + 64 bytes whose last 64 (the guard) are pre-filled with
+ * 'A' + i % 26, the kernel run on [0, n), all n + 64 bytes returned
+ * (out_n >= n + 64). */
+int wc_debug_translate(int device, const uint8_t* in, uint64_t n, const uint8_t map[256], uint8_t* out, uint64_t out_n);
 
 wc_engine* wc_engine_create(const wc_options* o);
 void wc_engine_destroy(wc_engine* e);
@@ -122,6 +140,9 @@ void wc_free(void* p);
 
 /* CPU paths */
 wc_result* wc_cpu_count(const uint8_t* text, uint64_t n, uint64_t global_base);
+/* The same on a copy of the text translated through `map` (checked as by
+ * wc_byte_map_check): the host twin of an engine with that byte map. */
+wc_result* wc_cpu_count_mapped(const uint8_t* text, uint64_t n, uint64_t global_base, const uint8_t map[256]);
 wc_result* wc_cpu_count_compat(const uint8_t* text, uint64_t n);
 /* Exact counts of n bytes of the synthetic stream from segment first_segment (offsets from
    global_base), computed from the generator's word walk on `threads` CPU threads (0 = all). */

@@ -70,7 +70,31 @@ struct Stats {
   // turn-arounds, H2D waits).  device_ms = their sum: first pass start to
   // finalize end.
   double map_ms = 0, reduce_ms = 0, finalize_ms = 0, merge_ms = 0, idle_ms = 0, device_ms = 0;
+  // wc_translate of every piece of text (Options::byte_map); part of device_ms,
+  // zero with no map set (no launch, no mark)
+  double translate_ms = 0;
 };
+
+// Byte map: a 256-entry translation table (as `tr`) applied to the text on the
+// GPU before it is tokenized.  Length-preserving, so first offsets, sharding,
+// chunking and echo keep their meaning; KeyTable::words are translated bytes.
+// Valid iff the three delimiters map to themselves (every cut made on raw
+// delimiters is still a token boundary of the translated text) and the map is
+// idempotent, m[m[b]] == m[b] (text translated twice stays correct: resident
+// text counted again, recovery re-runs).  Default: identity, off.
+struct ByteMap {
+  uint8_t m[256];
+  uint32_t on = 0;
+  ByteMap() {
+    for (int i = 0; i < 256; ++i) m[i] = (uint8_t)i;
+  }
+};
+// Empty if `m` is a valid map, else a message naming the offending byte.
+std::string byte_map_check(const uint8_t m[256]);
+// fold_case: A-Z -> a-z (ASCII only); split[0, split_n): each listed byte ->
+// space; split_punct: every ASCII punctuation byte (0x21-0x2F, 0x3A-0x40,
+// 0x5B-0x60, 0x7B-0x7E) -> space.  Valid by construction; `on` is set.
+ByteMap make_byte_map(bool fold_case, const uint8_t* split = nullptr, uint64_t split_n = 0, bool split_punct = false);
 
 struct Options {
   int device = 0;
@@ -101,6 +125,9 @@ struct Options {
   // Tests only: keep this many bits of the LONG-word (>= 16 bytes) tail hash
   // (0 = all 62) to force key collisions; equality stays exact (bytes compared).
   uint32_t k1_hash_bits = 0;
+  // Translate the text through this map before tokenizing (when byte_map.on);
+  // checked by the Engine constructor (byte_map_check).
+  ByteMap byte_map;
 };
 
 // Synthetic text spec (see src/kernels/synth.hpp).
@@ -140,6 +167,9 @@ class Engine {
 
   // Text already resident in HBM (16-B aligned).  Tokens owned by this call are
   // those starting in [0, n); bytes in [n, avail) may be read to finish them.
+  // With a byte map set, [0, avail) is REWRITTEN in place with the translated
+  // bytes (the const is kept for source compatibility): pass a buffer you own.
+  // prev_byte is the raw byte before d_text[0]; the engine translates it.
   void count_device(const uint8_t* d_text, uint64_t n, uint64_t avail, uint64_t global_base, int prev_byte = ' ');
   // Host text: staged through a pinned ring, H2D overlapped with compute.
   void count_host(const uint8_t* h_text, uint64_t n, uint64_t global_base);
@@ -189,7 +219,8 @@ class Engine {
 // ---- host components ----------------------------------------------------------
 namespace cpu {
 // Single-thread oracle (BASELINE config 1): hash map keyed by the word bytes.
-KeyTable count(const uint8_t* text, uint64_t n, uint64_t global_base = 0);
+// `map` (optional, used when map->on): counts a translated copy of the text.
+KeyTable count(const uint8_t* text, uint64_t n, uint64_t global_base = 0, const ByteMap* map = nullptr);
 // Exact counts of n bytes of the synthetic stream starting at segment
 // `first_segment`, offsets from global_base; `threads` workers (0 = all):
 // the full-scale benchmark oracle (words come from the generator's own walk).

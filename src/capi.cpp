@@ -6,6 +6,7 @@
 #include <exception>
 #include <memory>
 #include <thread>
+#include <vector>
 
 #include "common/hip_util.hpp"
 #include "dist/comm.hpp"
@@ -75,6 +76,8 @@ wc::Options to_opts(const wc_options* o) {
   x.records_per_byte = o->records_per_byte;
   x.merge_mode = o->merge_mode;
   x.k1_hash_bits = o->k1_hash_bits;
+  std::memcpy(x.byte_map.m, o->byte_map, 256);
+  x.byte_map.on = o->byte_map_on;
   return x;
 }
 
@@ -517,6 +520,52 @@ void wc_default_options(wc_options* o) {
   o->records_per_byte = d.records_per_byte;
   o->merge_mode = d.merge_mode;
   o->k1_hash_bits = d.k1_hash_bits;
+  std::memcpy(o->byte_map, d.byte_map.m, 256);  // identity
+  o->byte_map_on = d.byte_map.on;               // off
+}
+
+int wc_byte_map_check(const uint8_t m[256]) {
+  return guard([&] {
+    const std::string bad = wc::byte_map_check(m);
+    if (!bad.empty()) wc::fail(bad);
+  });
+}
+
+int wc_byte_map_build(int fold_case, const uint8_t* split, uint64_t split_n, int split_punct, uint8_t out[256]) {
+  return guard([&] {
+    const wc::ByteMap bm = wc::make_byte_map(fold_case != 0, split, split_n, split_punct != 0);
+    std::memcpy(out, bm.m, 256);
+  });
+}
+
+int wc_debug_translate(int device, const uint8_t* in, uint64_t n, const uint8_t map[256], uint8_t* out, uint64_t out_n) {
+  return guard([&] {
+    WC_CHECK(out_n >= n + 64, "wc_debug_translate: out must hold n + 64 bytes");
+    WC_HIP_CHECK(hipSetDevice(device));
+    wc::ByteMap bm;
+    std::memcpy(bm.m, map, 256);
+    bm.on = 1;
+    std::vector<uint8_t> h(n + 64);
+    if (n) std::memcpy(h.data(), in, n);
+    for (uint64_t i = 0; i < 64; ++i) h[n + i] = (uint8_t)('A' + i % 26);  // the guard: bytes a fold or a split would change
+    uint8_t* d = nullptr;
+    wc::dev_malloc(&d, n + 64);  // hipMalloc: 256-byte aligned
+    struct Free {
+      uint8_t* p;
+      ~Free() { (void)hipFree(p); }
+    } fr{d};
+    hipStream_t s = nullptr;
+    WC_HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+    hipError_t e = hipMemcpyAsync(d, h.data(), n + 64, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) {
+      wc::launch_translate(d, n, bm, s);
+      e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(out, d, n + 64, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    (void)hipStreamDestroy(s);
+    WC_HIP_CHECK(e);
+  });
 }
 
 wc_engine* wc_engine_create(const wc_options* o) {
@@ -551,6 +600,9 @@ wc_result* wc_count_file_checkpointed(wc_engine* e, const char* path, uint64_t b
                                       int world, const char* ckpt, uint64_t interval, int resume) {
   wc_result* r = nullptr;
   const int rc = guard([&] {
+    // the checkpoint file would have to record the map to resume under the same one
+    WC_CHECK(!(e && e->e->options().byte_map.on),
+             "checkpointed counting with a byte map is not supported (the checkpoint file does not record the map)");
     const std::string file(path), base(ckpt ? ckpt : "");
     const std::string cpath = base.empty() ? std::string() : wc::checkpoint_path(base, rank, world);
     wc::Checkpoint k = wc::open_checkpoint(cpath, resume != 0 && !cpath.empty(), file, wc::file_size(file), begin, end,
@@ -646,7 +698,7 @@ int wc_engine_stats_json(wc_engine* e, char* buf, int cap) {
                          "\"map_reruns\": %u, \"table_splits\": %u, \"log2_buckets\": %u, \"order_path\": %u, "
                          "\"merges_planned\": %u, \"merge_redos\": %u, \"download_bytes\": %llu, "
                          "\"device_ms\": {\"map\": %.4f, \"reduce\": %.4f, \"finalize\": %.4f, \"merge\": %.4f, "
-                         "\"idle\": %.4f, \"total\": %.4f}, "
+                         "\"idle\": %.4f, \"translate\": %.4f, \"total\": %.4f}, "
                          "\"host_ms\": {\"count\": %.4f, \"finalize\": %.4f, \"top_k\": %.4f, "
                          "\"word_order\": %.4f}, \"word_order\": {\"levels\": %u, \"unresolved\": %llu}}",
                          (unsigned long long)s.bytes, (unsigned long long)s.tokens, (unsigned long long)s.keys,
@@ -654,7 +706,7 @@ int wc_engine_stats_json(wc_engine* e, char* buf, int cap) {
                          s.map_reruns, s.table_splits, s.log2_buckets, s.order_path,
                          s.merges_planned, s.merge_redos, (unsigned long long)s.download_bytes,
                          s.map_ms,
-                         s.reduce_ms, s.finalize_ms, s.merge_ms, s.idle_ms, s.device_ms, s.host_count_ms,
+                         s.reduce_ms, s.finalize_ms, s.merge_ms, s.idle_ms, s.translate_ms, s.device_ms, s.host_count_ms,
                          s.host_finalize_ms, s.host_topk_ms, s.host_word_order_ms, s.word_order_levels,
                          (unsigned long long)s.word_order_unresolved);
   if (buf && cap > 0) {
@@ -713,6 +765,22 @@ void wc_free(void* p) { std::free(p); }
 wc_result* wc_cpu_count(const uint8_t* text, uint64_t n, uint64_t base) {
   wc_result* r = new wc_result;
   if (guard([&] { r->t = wc::cpu::count(text, n, base); }) != 0) {
+    delete r;
+    return nullptr;
+  }
+  return r;
+}
+
+wc_result* wc_cpu_count_mapped(const uint8_t* text, uint64_t n, uint64_t base, const uint8_t map[256]) {
+  wc_result* r = new wc_result;
+  if (guard([&] {
+        wc::ByteMap bm;
+        std::memcpy(bm.m, map, 256);
+        bm.on = 1;
+        const std::string bad = wc::byte_map_check(bm.m);
+        if (!bad.empty()) wc::fail(bad);
+        r->t = wc::cpu::count(text, n, base, &bm);
+      }) != 0) {
     delete r;
     return nullptr;
   }

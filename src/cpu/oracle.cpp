@@ -23,7 +23,13 @@
 namespace wc {
 namespace cpu {
 
-KeyTable count(const uint8_t* text, uint64_t n, uint64_t global_base) {
+KeyTable count(const uint8_t* text, uint64_t n, uint64_t global_base, const ByteMap* map) {
+  std::vector<uint8_t> mapped;  // the host twin of wc_translate: a translated copy, then the same count
+  if (map && map->on) {
+    mapped.resize(n);
+    for (uint64_t i = 0; i < n; ++i) mapped[i] = map->m[text[i]];
+    text = mapped.data();
+  }
   struct Ent {
     uint64_t count, first;
   };

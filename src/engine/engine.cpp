@@ -54,6 +54,10 @@ void TableStore::alloc(uint32_t log2_buckets) {
 
 // ---------------------------------------------------------------------- Impl --
 Engine::Impl::Impl(const Options& o) : opt(o) {
+  if (opt.byte_map.on) {
+    const std::string bad = byte_map_check(opt.byte_map.m);
+    if (!bad.empty()) fail(bad);
+  }
   dev = opt.device;
   WC_HIP_CHECK(hipSetDevice(dev));
   WC_HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
@@ -482,6 +486,18 @@ void Engine::Impl::launch_pass(const uint8_t* text, uint64_t len, uint64_t avail
   mark(EV_REDUCE);
 }
 
+void Engine::Impl::translate(uint8_t* text, uint64_t n) {
+  if (!opt.byte_map.on || n == 0) return;
+  mark(EV_PASS);  // closes the gap before it (idle), as a pass's first mark does
+  launch_translate(text, n, opt.byte_map, s);
+  mark(EV_TRANSLATE);
+  if (sync_debug) {
+    const hipError_t e = hipStreamSynchronize(s);
+    fprintf(stderr, "[wc] translate n=%llu -> %s\n", (unsigned long long)n, hipGetErrorString(e));
+    WC_HIP_CHECK(e);
+  }
+}
+
 void Engine::Impl::check_table(const char* where) {
   if (!d_tab_err) return;
   launch_check_table(table(), d_tab_err, s);
@@ -534,7 +550,7 @@ void Engine::Impl::mark(int tag) {
 // consecutive marks, charged to the stage the later mark closes.
 void Engine::Impl::collect_stage_times() {
   if (ev_n < 2) return;
-  double t[EV_FIN_END + 1] = {};
+  double t[EV_COUNT] = {};
   for (size_t i = 1; i < ev_n; ++i) {
     float ms = 0;
     if (hipEventElapsedTime(&ms, ev_pool[i - 1], ev_pool[i]) != hipSuccess) {
@@ -548,7 +564,8 @@ void Engine::Impl::collect_stage_times() {
   st.merge_ms = t[EV_MERGE1];
   st.finalize_ms = t[EV_MERGE0] + t[EV_FIN_END];
   st.idle_ms = t[EV_PASS] + t[EV_FIN];
-  st.device_ms = st.map_ms + st.reduce_ms + st.merge_ms + st.finalize_ms + st.idle_ms;
+  st.translate_ms = t[EV_TRANSLATE];
+  st.device_ms = st.map_ms + st.reduce_ms + st.merge_ms + st.finalize_ms + st.idle_ms + st.translate_ms;
 }
 
 void Engine::Impl::drop_reduce_bits() {
@@ -1358,6 +1375,15 @@ void Engine::count_device(const uint8_t* d_text, uint64_t n, uint64_t avail, uin
   Range r("wc_count_device");
   const double t0 = now_seconds();
   const uint64_t C = im.opt.chunk_bytes;
+  if (im.opt.byte_map.on && n) {
+    // once, before the chunk loop, and all of [0, avail): the map reads past a
+    // chunk's len into the next chunk (and past n) to finish a token.  A pass
+    // still pending on this text settles first; its re-runs would read the
+    // same bytes either way (the map is idempotent).
+    im.settle();
+    im.translate(const_cast<uint8_t*>(d_text), avail);
+    prev_byte = im.map_prev(prev_byte);
+  }
   for (uint64_t off = 0; off < n; off += C) {
     const uint64_t len = std::min<uint64_t>(C, n - off);
     im.process_chunk(d_text + off, len, avail - off, global_base + off, off == 0 ? prev_byte : -1, off + len >= n);
@@ -1428,6 +1454,7 @@ void Engine::count_source(ChunkSource& src, uint64_t global_base) {
     im.giant_mem.reset();
     uint8_t* d = static_cast<uint8_t*>(im.giant_mem.take(n + 4096));
     WC_HIP_CHECK(hipMemcpy(d, giant.data(), n, hipMemcpyHostToDevice));
+    im.translate(d, n);  // no raw delimiter in it, but the map may split it into many words: an ordinary pass
     const uint32_t blocks = im.blocks_for(n), rb = im.rec_buckets_log2();
     im.launch_pass(d, n, n, base, ' ', rb, blocks);
     im.complete_pass(d, n, n, base, ' ', rb, blocks);
@@ -1497,9 +1524,10 @@ void Engine::count_source(ChunkSource& src, uint64_t global_base) {
   double t_fill = 0, t_launch = 0, t_wait = 0;
   const double t_pre = now_seconds() - t0;  // staging ring + the first piece's read
   for (uint64_t k = 0; len; ++k) {
-    const uint8_t* d = im.d_stage[k & 1];
+    uint8_t* d = im.d_stage[k & 1];
     const double a0 = trace ? now_seconds() : 0;
     WC_HIP_CHECK(hipStreamWaitEvent(im.s, im.ev_h2d[k & 1], 0));
+    im.translate(d, len);
     const uint32_t blocks = im.blocks_for(len);
     const uint32_t rb = im.rec_buckets_log2();
     im.launch_pass(d, len, len, offset, ' ', rb, blocks);
@@ -1563,8 +1591,9 @@ void Engine::count_pinned_replay(const uint8_t* pool, uint64_t pool_bytes, uint6
   if (nchunks) issue(0);
   for (uint64_t k = 0; k < nchunks; ++k) {
     const uint64_t len = std::min<uint64_t>(C, total - k * C);
-    const uint8_t* d = im.d_stage[k & 1];
+    uint8_t* d = im.d_stage[k & 1];
     WC_HIP_CHECK(hipStreamWaitEvent(im.s, im.ev_h2d[k & 1], 0));
+    im.translate(d, len);
     const uint32_t blocks = im.blocks_for(len), rb = im.rec_buckets_log2();
     // a truncated last chunk may end mid-word: it is the end of the stream
     im.launch_pass(d, len, len, global_base + k * C, ' ', rb, blocks);

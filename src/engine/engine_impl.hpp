@@ -254,7 +254,7 @@ struct Engine::Impl {
   // Stage events (device time per stage of the last job, Stats::map_ms ...):
   // mark(tag) records an event on s; the interval from the previous mark to
   // this one is charged to the stage `tag` closes.
-  enum : int { EV_PASS = 0, EV_MAP, EV_REDUCE, EV_FIN, EV_MERGE0, EV_MERGE1, EV_FIN_END };
+  enum : int { EV_PASS = 0, EV_MAP, EV_REDUCE, EV_FIN, EV_MERGE0, EV_MERGE1, EV_FIN_END, EV_TRANSLATE, EV_COUNT };
   bool stage_events = true;
   std::vector<hipEvent_t> ev_pool;
   std::vector<int> ev_tag;
@@ -263,6 +263,13 @@ struct Engine::Impl {
   void mark(int tag);
   void collect_stage_times();
   uint32_t blocks_for(uint64_t len) const;
+  // Options::byte_map: text[0, n) through the map, in place, on stream s —
+  // called where a piece of text becomes device-resident, outside launch_pass,
+  // so a pass's recovery re-runs reuse the translated text.  Charged to
+  // Stats::translate_ms.  No map set: nothing is launched and nothing marked.
+  void translate(uint8_t* text, uint64_t n);
+  // the raw byte before a piece (or -1) as the tokenizer must see it
+  int map_prev(int prev) const { return opt.byte_map.on && prev >= 0 ? (int)opt.byte_map.m[prev & 0xFF] : prev; }
   // Shuffle partitions track the running table (one reduce block reads only
   // its own partition) up to MAX_REC_BUCKETS.
   uint32_t rec_shift = 0;  // WC_REC_SHIFT (sweeps only): shuffle partitions = table buckets >> shift

@@ -9,6 +9,7 @@
 //   wc_topk_*         the K most frequent rows of the ordered table (Engine::top_k)
 //   wc_word_*         the ordered table's rows by word, bytewise (Engine::result_by_word)
 //   wc_synth_text     device-side synthetic text generator
+//   wc_translate      device text through a 256-entry byte map, in place (Options::byte_map)
 // Reference counterparts: mapKernel (/root/reference/main.cu:109-117) and the
 // single-thread reduceKernel (main.cu:119-123).
 #pragma once
@@ -631,6 +632,12 @@ void launch_scatter_ids(const uint32_t* send_pos, const uint32_t* ids_back, cons
                         const unsigned long long* owns, uint32_t W, const uint64_t* cnt, const uint64_t* first,
                         uint64_t n, uint64_t* dcnt, uint64_t* dfirst, hipStream_t s, const uint64_t* dn = nullptr,
                         uint64_t pad = 0);  // ids_back: owner-local; pad > 0: padded ids (owner base o * pad)
+
+// ---- byte map (src/kernels/translate.hip) ----
+// text[i] = map.m[text[i]] for i in [0, n), in place: text 16-byte aligned, n
+// arbitrary, no byte at or beyond n is written.  n == 0: no launch.
+struct ByteMap;  // wc/wc.hpp
+void launch_translate(uint8_t* text, uint64_t n, const ByteMap& map, hipStream_t s);
 
 // ---- stream-ordered loopback communicator (src/kernels/comm.hip, dist/comm.cpp) ----
 constexpr int LB_MAX_RANKS = 64, LB_RING = 16, LB_XFER_PARTS = 64;

@@ -40,6 +40,13 @@ const char* kUsage =
     "  --sort first|word       row order: first occurrence (default, as the reference) or\n"
     "                          plain bytewise order of the words (sort | uniq -c; GPU paths:\n"
     "                          ordered on the device); not together with --top K\n"
+    "  --fold-case             count A-Z as a-z (ASCII only): the text is translated through a\n"
+    "                          byte map before it is tokenized (GPU paths: on the device);\n"
+    "                          listed words are the translated bytes, the echo stays raw\n"
+    "  --split-punct           every ASCII punctuation byte splits words, as a space does\n"
+    "  --split BYTES           each of BYTES splits words; C escapes \\t \\n \\xHH \\\\ are read\n"
+    "                          (the three map flags combine; not with --compat=reference or\n"
+    "                          --checkpoint)\n"
     "  --synthetic SIZE[:SEED[:VOCAB[:ZIPF[:LONGFRAC]]]]  count generated text instead of FILE\n"
     "  --chunk-bytes N         device chunk size (default 1G)\n"
     "  --host-staged           stream FILE through the pinned host ring (no echo)\n"
@@ -66,6 +73,40 @@ uint64_t parse_size(const std::string& s) {
   return (uint64_t)(v * (double)mul);
 }
 
+// --split BYTES: the bytes themselves, with the C escapes \t \n \r \0 \\ \xHH read.
+std::string parse_bytes(const std::string& s) {
+  std::string out;
+  for (size_t i = 0; i < s.size(); ++i) {
+    if (s[i] != '\\') {
+      out.push_back(s[i]);
+      continue;
+    }
+    if (++i >= s.size()) wc::fail("--split: a lone backslash at the end of " + s);
+    auto hex = [&](char c) -> int {
+      if (c >= '0' && c <= '9') return c - '0';
+      if (c >= 'a' && c <= 'f') return c - 'a' + 10;
+      if (c >= 'A' && c <= 'F') return c - 'A' + 10;
+      return -1;
+    };
+    switch (s[i]) {
+      case 't': out.push_back('\t'); break;
+      case 'n': out.push_back('\n'); break;
+      case 'r': out.push_back('\r'); break;
+      case '0': out.push_back('\0'); break;
+      case '\\': out.push_back('\\'); break;
+      case 'x': {
+        if (i + 2 >= s.size() || hex(s[i + 1]) < 0 || hex(s[i + 2]) < 0)
+          wc::fail("--split: \\x needs two hex digits in " + s);
+        out.push_back((char)(hex(s[i + 1]) * 16 + hex(s[i + 2])));
+        i += 2;
+        break;
+      }
+      default: wc::fail(std::string("--split: unknown escape \\") + s[i] + " in " + s);
+    }
+  }
+  return out;
+}
+
 struct Cli {
   std::string file = "test.txt";
   int gpus = 1;
@@ -82,6 +123,9 @@ struct Cli {
   std::string ckpt;
   uint64_t ckpt_every = 4ull << 30;
   bool resume = false;
+  bool fold_case = false, split_punct = false;
+  std::string split;   // --split, escapes resolved
+  wc::ByteMap map;     // built from the three flags; on when any was given
 };
 
 Cli parse(int argc, char** argv) {
@@ -122,6 +166,9 @@ Cli parse(int argc, char** argv) {
     else if (a == "--checkpoint") c.ckpt = need("--checkpoint");
     else if (a == "--checkpoint-every") c.ckpt_every = parse_size(need("--checkpoint-every"));
     else if (a == "--resume") c.resume = true;
+    else if (a == "--fold-case") c.fold_case = true;
+    else if (a == "--split-punct") c.split_punct = true;
+    else if (a == "--split") c.split += parse_bytes(need("--split"));
     else if (a == "--synthetic") {
       std::string v = need("--synthetic");
       std::vector<std::string> f;
@@ -140,6 +187,16 @@ Cli parse(int argc, char** argv) {
   if (c.synthetic) c.echo = false;
   if (!c.ckpt.empty() && (c.synthetic || c.compat)) wc::fail("--checkpoint needs a FILE input and the clean semantics");
   if (c.resume && c.ckpt.empty()) wc::fail("--resume needs --checkpoint PATH");
+  if (c.fold_case || c.split_punct || !c.split.empty()) {
+    if (c.compat)
+      wc::fail("--fold-case / --split-punct / --split cannot be combined with --compat=reference (the reference "
+               "program has no byte map)");
+    if (!c.ckpt.empty())
+      wc::fail("--fold-case / --split-punct / --split cannot be combined with --checkpoint (the checkpoint file "
+               "does not record the map)");
+    c.map = wc::make_byte_map(c.fold_case, reinterpret_cast<const uint8_t*>(c.split.data()), c.split.size(),
+                              c.split_punct);
+  }
   if (c.sort_word && c.top > 0)
     wc::fail("--sort word cannot be combined with --top K: --top lists by count (the K most frequent words in "
              "word order is not implemented)");
@@ -218,7 +275,7 @@ int run(const Cli& c) {
         t = wc::cpu::count_reference_compat(p, host.size(), &echoed);
         if (have_text) text = std::move(echoed);  // the reference echoes only the records it read
       } else {
-        t = wc::cpu::count(p, host.size());
+        t = wc::cpu::count(p, host.size(), 0, &c.map);  // translated on the host
       }
     }
     bytes = host.size();
@@ -248,6 +305,7 @@ int run(const Cli& c) {
         o.device = devs[r];
         o.chunk_bytes = c.chunk;
         o.merge_mode = c.merge_mode;
+        o.byte_map = c.map;  // every GPU path below: translated on the device
         wc::Engine eng(o);
         if (!c.ckpt.empty()) {
           // Checkpointed: delimiter-aligned intervals, each finalised on the GPU and
